@@ -2,22 +2,32 @@
 """Benchmark of the hot path: candidate trajectories / s (sample + convert + check + cost + collide
 + select) per replanning step, through the C ABI of librp_amd.so.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--mode draw|materialize|fused]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--mode draw|materialize|fused] [--full]
+                    [--dump-outputs DIR]
+
+A plain run (N = 1) sets up, warms up, times exactly K steps, writes the last step's outputs if ``--dump-outputs`` is given and
+prints the line: nothing else.  ``--full`` adds every record beside the headline (listed below) and the detail file.
 
 One *step* = one ``rp_plan`` call over the whole candidate batch of one replanning cycle (grids and parameters staged
 host->device inside the call: a few hundred bytes; tables resident), including the winner's state block coming back to
 the host.  Consecutive steps are consecutive cycles of a REPLANNING SEQUENCE (``workloads.replan_sequence``: the scenario
 driven in closed loop, every step a new initial state, velocity grid and time index; cfg5: a seeded list of initial
-states), not one repeated input.  A timed region is exactly K steps; regions are repeated until at least
-``--min-seconds`` of timed work has accumulated, ``ms_per_step`` is the median region, the spread is reported.
+states), not one repeated input.  A timed region is exactly K steps.  The N = 1 headline is ONE region (``--steps`` sets the
+number of timed steps; ``ms_per_step`` = its time / K) unless ``--min-seconds`` is given; every other record repeats its regions
+until ``--min-seconds`` (default 0.5 s) of timed work has accumulated, ``ms_per_step`` is the median region, the spread is reported.
 
-N = 1 (default): headline = cfg3 (BASELINE.json configs[2], the largest configuration tagged 1 x MI355X) in draw mode, plus --
-in the detail file, their key numbers in the line --
+``--dump-outputs DIR``: after the headline's timed steps, what its last step handed the caller (rp_result, the winner's state block,
+status of every candidate, cost of every candidate that has one, the state rows of a seeded sample of 256 candidates in draw mode)
+as DIR/<name>.npy, float64, every value finite (``dump_outputs``).
+
+N = 1 (default): headline = cfg3 (BASELINE.json configs[2], the largest configuration tagged 1 x MI355X) in draw mode, plus, with
+``--full`` -- in the detail file, their key numbers in the line --
   ``configs``          draw- and production-mode records of cfg1, cfg2, cfg3f (cfg3's grid in mostly-free traffic), <cfg>rb (cfg2, cfg3, cfg3f, cfg4 with the road boundary),
                        cfg4, cfg5, each with its own roofline
   ``fused_mode``       the headline workload in production mode (12 B per candidate leave the kernel)
   ``plan_latency_ms``  p50 / p90 of ReactivePlanner.plan() over closed-loop replans (Python boundary included)
   ``cpu_baseline``     the C port of the reference algorithm (oracle/) on the host cores, bounded sample
+  ``level_loop_latency_ms``, ``corridor_sampling``, ``python_binding``: further records
 N > 1: one process per GPU (the driver's ``python -m torch.distributed.run ... bench.py --gpus N``; started without a
   launcher, this script starts the N ranks itself as child processes BEFORE anything touches the GPU and relays rank
   0's line).  Headline = WEAK scaling of the N = 1 workload: the grid's longitudinal samples densified N times, every rank
@@ -25,12 +35,13 @@ N > 1: one process per GPU (the driver's ``python -m torch.distributed.run ... b
   `--gpus 1` -- and the ranks exchange one {cost, index, counters, winner block} message per step
   (commonroad_rp_amd/distributed.py; no data-path collective).  Beside it (`strong`): BASELINE.json configs[3], cfg4's
   512 064-candidate grid cut into N ranges, the same regions with the other exchange transport, the exchange time per step
-  of both, rank 0 alone on the whole grid.  `--scaling strong` makes that record the headline.
+  of both, rank 0 alone on the whole grid.  `--scaling strong` makes that record the headline.  N > 1 measures all of these
+  records with or without ``--full``.
 
-Prints ONE JSON line (rank 0): the COMPACT record (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, p50 / p90 of plan(), one
-number pair per side configuration, the N > 1 exchange keys); the full record of the run (every side record with its spread, roofline
-and description) is written to `gpurun_out/bench_detail_n<N>.json` (the repo root without that directory) and named in the line's
-`detail`.  Modes:
+Prints ONE JSON line (rank 0): the COMPACT record (< 4 KB: the contract's keys, `roofline`; with ``--full`` or N > 1 also
+`cpu_baseline`, p50 / p90 of plan(), one number pair per side configuration, the N > 1 exchange keys); the full record of such a run
+(every side record with its spread, roofline and description) is written to ``bench_detail_n<N>.json`` (``emit``) and named in the
+line's `detail`.  Modes:
   draw        every candidate fully evaluated (no pre-filter / early exit, the reference's draw_traj_set semantics)
               and all 14 state rows of every candidate written to HBM.  Default: work per candidate is data independent
               and the byte count is SURVEY 8(d)'s bytes = C*12 + C*112*(N+1) + 112*(N+1).
@@ -71,7 +82,9 @@ def parse_args():
     ap.add_argument("--scaling", default="weak", choices=["strong", "weak"],
                     help="N > 1: which record is the headline -- weak: every rank a shard the size of the N = 1 workload (its longitudinal "
                          "grid densified N times), the same per-GPU work as `--gpus 1`; strong: cfg4's grid cut into N ranges")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="timed work per measured record (regions of K steps are repeated)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="timed work per measured record (regions of K steps are repeated); default: the N = 1 headline times one "
+                         "region of K steps, every other record 0.5 s")
     ap.add_argument("--sequence", type=int, default=32, help="replanning cycles in the input sequence")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -80,7 +93,20 @@ def parse_args():
                     help="only the timed region of the headline (no other leg): counter passes")
     ap.add_argument("--road-boundary", action="store_true",
                     help="scenario workloads: add the road boundary (thin rectangles, collision.road_boundary_obb) to the obstacle tables")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: every record beside the headline (side configurations, production mode, plan() latencies, corridor "
+                         "sampling, Python binding, CPU baseline) and the detail file; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the headline's last timed step computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: one-GPU runs only")
+    return args
+
+
+def side_seconds(args) -> float:
+    """--min-seconds of every record but the N = 1 headline"""
+    return 0.5 if args.min_seconds is None else args.min_seconds
 
 
 def main():
@@ -102,7 +128,14 @@ def main():
         os.dup2(real_stdout, 1)
         os.close(real_stdout)
     if result is not None:
-        print(emit(result, args), flush=True)
+        print(bench_line(result, args), flush=True)
+
+
+def bench_line(result: dict, args) -> str:
+    """The line a run prints: with --full (or N > 1) ``emit`` -- detail file written and named --, else the compact record alone."""
+    if getattr(args, "full", False) or result.get("n_gpus", 1) > 1:
+        return emit(result, args)
+    return json.dumps(compact_line(result), separators=(",", ":"))
 
 
 def self_launch(args) -> int:
@@ -236,9 +269,10 @@ def roofline_record(name, mode, n_steps_plus1, cand_mean, feasible_mean, kernel_
             "kernel": kernel, "kernel_ms": kernel_ms, "bytes_per_launch": bytes_per_launch, **extra}
 
 
-def run_record(ctx, w, seq, mode, steps, warmup, min_seconds, sync, name=None, profile_every=8, caller="c"):
+def run_record(ctx, w, seq, mode, steps, warmup, min_seconds, sync, name=None, profile_every=8, caller="c", dump=None):
     """One measured record on one GPU: the sequence in one mode.  ``caller``: who calls rp_plan inside the timed regions --
-    "c": a compiled host loop over the C ABI (csrc/rp_hostloop.c), "python": the ctypes binding, one ``ctx.plan`` per step."""
+    "c": a compiled host loop over the C ABI (csrc/rp_hostloop.c), "python": the ctypes binding, one ``ctx.plan`` per step.
+    ``dump``: directory for the outputs of the last timed step (dump_outputs)."""
     from commonroad_rp_amd._capi import HostLoop
     inputs = with_mode(seq, mode)
     kms, feas, paths = [], [], [0, 0, 0, 0]
@@ -262,6 +296,9 @@ def run_record(ctx, w, seq, mode, steps, warmup, min_seconds, sync, name=None, p
                 paths[i] += st.paths[i]
     regions = measure(step, len(inputs), steps, warmup, min_seconds, sync, region=region)
     ctx.set_profiling(0)
+    if dump:
+        from commonroad_rp_amd._capi import PlanOutput
+        dump_outputs(dump, ctx, PlanOutput.from_c(ctx._res, loop.best_states() if region is not None else ctx._last_best), mode)
     sp = spread(regions)
     cand = float(np.mean([q.n_candidates for q in inputs]))
     if region is not None:
@@ -277,6 +314,61 @@ def run_record(ctx, w, seq, mode, steps, warmup, min_seconds, sync, name=None, p
            "roofline": roofline_record(name or w.name, mode, n1, cand, float(np.mean(feas)) if feas else 0.0, kernel_ms,
                                        kernel=ctx.last_kernel())}
     return rec
+
+
+DUMP_STATE_SAMPLE = 256        # candidates whose state rows a draw-mode dump holds (seeded choice)
+DUMP_MAX_CANDIDATES = 1 << 20  # per-candidate arrays of larger batches: a seeded sample of this many candidates
+
+
+def dump_outputs(path, ctx, out, mode):
+    """What the last plan on ``ctx`` handed its caller (``out``: its PlanOutput), as ``path/<name>.npy`` (float64, every value finite;
+    a few MB for cfg3, < 64 MB for any workload):
+      best_index, counts = [n_candidates, n_feasible, n_collision, n_collision_before_best], reason_counts  (rp_result; kernel_ms,
+                   a timing, is left out)
+      best_cost, best_coeffs = [lon 6, lat 6, lat_T], best_states [14, N + 1]  (the winner's: only written when there is one)
+      status       status word of every candidate (rp_fetch_status)
+      cost, cost_index  the cost of every candidate that has one (rp_fetch_status reports NaN for the others) and its index
+      states_sample, states_sample_index  draw mode (every state block kept on the device): the state rows of a seeded sample of
+                   candidates whose rows are finite (rp_fetch_states) -- the first DUMP_STATE_SAMPLE of a fixed permutation that are
+                   finite in the build that wrote the dump, so two builds that disagree on a row's finiteness sample different
+                   candidates: compare such dumps row by row on the indices both states_sample_index arrays hold
+    Batches beyond DUMP_MAX_CANDIDATES: status and cost of a seeded sample of candidates (candidate_index)."""
+    os.makedirs(path, exist_ok=True)
+    C = int(out.n_candidates)
+    arrays = {
+        "best_index": [out.best_index],
+        "counts": [out.n_candidates, out.n_feasible, out.n_collision, out.n_collision_before_best],
+        "reason_counts": out.reason_counts,
+    }
+    if out.best_index >= 0:
+        arrays["best_cost"] = [out.best_cost]
+        arrays["best_coeffs"] = np.concatenate([out.best_lon_coeffs, out.best_lat_coeffs, [out.best_lat_T]])
+        arrays["best_states"] = out.best_states
+    status, cost = ctx.fetch_status()
+    idx = np.arange(C)
+    if C > DUMP_MAX_CANDIDATES:
+        idx = np.sort(np.random.default_rng(0).choice(C, DUMP_MAX_CANDIDATES, replace=False))
+        status, cost = status[idx], cost[idx]
+        arrays["candidate_index"] = idx
+    has = np.isfinite(cost)
+    arrays["status"], arrays["cost"], arrays["cost_index"] = status, cost[has], idx[has]
+    if mode == "draw" and C > 0:
+        rows, picked = [], []
+        for i in np.random.default_rng(1).permutation(C)[:16 * DUMP_STATE_SAMPLE]:
+            r = ctx.fetch_states(int(i), 1)[0]
+            if np.all(np.isfinite(r)):
+                rows.append(r)
+                picked.append(int(i))
+                if len(rows) == DUMP_STATE_SAMPLE:
+                    break
+        order = np.argsort(picked)
+        arrays["states_sample"] = np.asarray(rows)[order] if rows else np.empty((0, 14, 0))
+        arrays["states_sample_index"] = np.asarray(picked)[order]
+    for k, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if not np.all(np.isfinite(a)):
+            raise RuntimeError(f"--dump-outputs: {k} holds a value that is not finite")
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def steps_for(ms_guess, steps):
@@ -426,7 +518,8 @@ def run_single(args, torch, device):
     seq = W.replan_sequence(base, args.sequence, device=device)
     base.setup(ctx)
     key = name + ("rb" if args.road_boundary else "")   # (the counter files' key of this workload)
-    head = run_record(ctx, base, seq, args.mode, args.steps, args.warmup, args.min_seconds, sync, name=key, caller=args.caller)
+    head = run_record(ctx, base, seq, args.mode, args.steps, args.warmup, args.min_seconds or 0.0, sync, name=key, caller=args.caller,
+                      dump=args.dump_outputs)
     N = base.inputs.params.N
     result = {
         "metric": "candidate trajectories/sec (sample+cost+collision) per replan",
@@ -438,7 +531,8 @@ def run_single(args, torch, device):
                    "horizon_steps": N, "n_obstacles": int(base.obstacles.dyn_obb.shape[0] + len(base.obstacles.static_obb)),
                    "inputs": f"replanning sequence of {len(seq)} consecutive cycles (closed loop over the scenario; cfg5: seeded initial states)",
                    "parallelism": "one GPU", "exchange": "none"},
-        "timing": dict(head["spread_ms"], what="K-step regions bracketed by device syncs, repeated until min-seconds; ms_per_step = median region",
+        "timing": dict(head["spread_ms"], what="one K-step region bracketed by device syncs (with --min-seconds: repeated until that much timed "
+                                               "work; ms_per_step = median region)",
                        caller=head["caller"]),
         "roofline": head["roofline"],
         # what "value" has meant round by round (rounds 1-2 are not comparable with 3-4 on `value`; the riders keep the old lines)
@@ -448,12 +542,12 @@ def run_single(args, torch, device):
                                                  "n_gpus_gt_1": "strong scaling on cfg4"},
                                 "old_definition_rides_in": ["configs.cfg2", "python_binding", "strong"]},
     }
-    if not args.main_only:
+    if args.full and not args.main_only:
         if args.caller == "c":   # the same regions with the Python binding making the calls (what round 1 and 2 reported)
-            py = run_record(ctx, base, seq, args.mode, args.steps, args.warmup, min(args.min_seconds, 0.5), sync, name=key, caller="python")
+            py = run_record(ctx, base, seq, args.mode, args.steps, args.warmup, min(side_seconds(args), 0.5), sync, name=key, caller="python")
             result["python_binding"] = {k: py[k] for k in ("ms_per_step", "value", "unit", "caller", "kernel_ms")}
         if args.mode != "fused":
-            result["fused_mode"] = run_record(ctx, base, seq, "fused", args.steps, args.warmup, args.min_seconds, sync, name=key)
+            result["fused_mode"] = run_record(ctx, base, seq, "fused", args.steps, args.warmup, side_seconds(args), sync, name=key)
         ctx.close()
         ctx = None
         if not args.no_configs:
@@ -494,7 +588,7 @@ def side_configs(args, torch, device, skip):
         rec = {"workload": f"{w.name}: {w.description}", "horizon_steps": int(w.inputs.params.N)}
         for mode in ("draw", "fused"):
             k = steps_for(guess[name] * (1.0 if mode == "draw" else 0.5), args.steps)
-            rec[mode] = run_record(ctx, w, seq, mode, k, 3, args.min_seconds, torch.cuda.synchronize, name=name)
+            rec[mode] = run_record(ctx, w, seq, mode, k, 3, side_seconds(args), torch.cuda.synchronize, name=name)
         ctx.close()
         out[name] = rec
     return out
@@ -712,7 +806,7 @@ def run_multi(args, torch, dist, rank, local_rank, world, rehearse):
             def region(k0, n):
                 st, tex = loop.run_sharded(ex, k0, n)
                 tot["kms"] += st.kernel_ms_sum; tot["kn"] += st.kernel_ms_n; tot["tex"] += tex; tot["n"] += n
-        regions = measure(step, len(inputs), steps, args.warmup, args.min_seconds, sync, bar, region=region)
+        regions = measure(step, len(inputs), steps, args.warmup, side_seconds(args), sync, bar, region=region)
         ctx.set_profiling(0)
         sp = spread(regions)
         cand = float(np.mean([q.n_candidates for q in inputs]))
@@ -754,7 +848,7 @@ def run_multi(args, torch, dist, rank, local_rank, world, rehearse):
     # rank 0 alone on the whole grid: the N = 1 point of the same workload, measured in the same run
     alone = None
     if rank == 0:
-        alone = run_record(ctx, ws, seq_s, args.mode, steps_for(1.8, args.steps), 3, args.min_seconds, sync, caller=args.caller)   # (same caller as the sharded steps)
+        alone = run_record(ctx, ws, seq_s, args.mode, steps_for(1.8, args.steps), 3, side_seconds(args), sync, caller=args.caller)   # (same caller as the sharded steps)
     dist.barrier()
     # ---- weak scaling: every rank a shard the size of the N = 1 headline workload (its longitudinal grid densified N times):
     #      per-GPU work as in `bench.py --gpus 1`, so that the per-N values of a scaling run refer to the same unit of work
@@ -771,7 +865,7 @@ def run_multi(args, torch, dist, rank, local_rank, world, rehearse):
     alone_w = None
     if rank == 0:
         ww.setup(ctx)
-        alone_w = run_record(ctx, ww, seq_1, args.mode, args.steps, 3, args.min_seconds, sync, caller=args.caller)
+        alone_w = run_record(ctx, ww, seq_1, args.mode, args.steps, 3, side_seconds(args), sync, caller=args.caller)
     dist.barrier()
     # ranks RCCL itself carried data for: an all-reduce of ones over the nccl group (0 in a gloo rehearsal)
     rccl_ranks = 0

@@ -9,7 +9,7 @@ Two pieces:
     the reference planner already has (``config, dt, N, horizon, vehicle_params, x_0, _co,
     sampling_space, cost_function, _low_vel_mode, _draw_traj_set, ...``), so it can be mixed into the
     reference class itself: ``class Planner(GpuBackendMixin, commonroad_rp.reactive_planner.ReactivePlanner)``
-    (exercised against the real reference class in tests/test_planner_dropin.py).
+    (INTEGRATION.md).
 
 ``ReactivePlanner``
     A stand-alone planner with the reference's public surface (``reset, set_reference_path,

@@ -14,5 +14,5 @@ rm -rf $OUT/trace
 cd $ROOT
 [ -f $LIBDIR/librp_amd_tl.so ] && RP_AMD_LIBRARY=$LIBDIR/librp_amd_tl.so RP_AMD_PRINT_STAMPS=1 python3 profiles/probe_stamps_cfg3.py $WL > $OUT/wg_timeline.txt 2>&1
 [ -f $LIBDIR/librp_amd_st.so ] && RP_AMD_LIBRARY=$LIBDIR/librp_amd_st.so RP_AMD_PRINT_STAMPS=1 python3 profiles/probe_stamps_cfg3.py $WL > $OUT/stamps.txt 2>&1
-python3 bench.py --workload $WL --mode $MODE --no-cpu-baseline --no-configs --min-seconds 0.3 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --workload $WL --mode $MODE --no-cpu-baseline --no-configs --min-seconds 0.3 > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/step_timeline.txt $OUT/trace_summary.txt; tail -4 $OUT/wg_timeline.txt; tail -6 $OUT/stamps.txt

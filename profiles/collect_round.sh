@@ -7,6 +7,7 @@ TAG=${1:-r02x}; QUICK=${2:-}
 ROOT=$GRAFT_REPO_ROOT; OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
+# (--min-seconds 0.5: the headline repeats its K-step regions for 0.5 s, as the records of earlier rounds did; a plain run times one region)
 # counters first: the bench line below then carries `traffic` and the FP64 fraction of this very code (bench.py reports the
 # numbers of profiles/r05_*.json only when their source hash is the library's)
 if [ -z "$QUICK" ]; then
@@ -19,22 +20,22 @@ for wl in cfg1 cfg2 cfg2rb cfg3 cfg3rb cfg3f cfg3frb cfg4 cfg4rb cfg5; do
 done
 cp profiles/r05_pmc_traffic.json profiles/r05_fp64_flops.json $OUT/
 fi
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 bench.py --full --min-seconds 0.5 > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 cp gpurun_out/bench_detail_n1.json $OUT/${TAG}_bench_detail.json
 # cfg2 as the headline workload (the headline of rounds 1-2; carries plan() latency on cfg2)
-python3 bench.py --workload cfg2 --no-configs --no-cpu-baseline > $OUT/${TAG}_bench_cfg2.json 2>> $OUT/bench.err
+python3 bench.py --full --min-seconds 0.5 --workload cfg2 --no-configs --no-cpu-baseline > $OUT/${TAG}_bench_cfg2.json 2>> $OUT/bench.err
 cp gpurun_out/bench_detail_n1.json $OUT/${TAG}_bench_cfg2_detail.json
 # plan() in closed loop with the cycle's call made by the binding's extension module / through ctypes, on this box
 python3 profiles/probe_plan_latency_r05.py cfg2 cfg1 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_plan_latency_ab.txt
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --full --min-seconds 0.5 --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err
 cp $(ls $OUT/prof/*/*kernel_stats.csv | head -1) $OUT/${TAG}_kernel_stats.csv
 python3 $ROOT/profiles/summarize_trace.py $(ls $OUT/prof/*/*kernel_trace.csv | head -1) > $OUT/${TAG}_kernel_trace_summary.txt
 rm -rf $OUT/prof
 # the headline alone (no side configurations: cfg3rb / cfg3frb launch the same kernel instance on the same grid as the headline, so
 # the averages of the full line's trace mix three workloads): the kernel durations bench.py's headline `kernel_ms` has to agree with
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --no-cpu-baseline --no-configs > $OUT/${TAG}_headline_bench_under_rocprof.json 2>> $OUT/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --full --min-seconds 0.5 --no-cpu-baseline --no-configs > $OUT/${TAG}_headline_bench_under_rocprof.json 2>> $OUT/prof.err
 python3 $ROOT/profiles/summarize_trace.py $(ls $OUT/prof/*/*kernel_trace.csv | head -1) > $OUT/${TAG}_headline_kernel_trace_summary.txt
 python3 $ROOT/profiles/step_timeline.py $(ls $OUT/prof/*/*kernel_trace.csv | head -1) > $OUT/${TAG}_headline_step_timeline.txt 2>&1 || true
 python3 $ROOT/profiles/step_timeline.py $(ls $OUT/prof/*/*kernel_trace.csv | head -1) production > $OUT/${TAG}_production_step_timeline.txt 2>&1 || true

@@ -169,3 +169,42 @@ def record_plan_stats(planner):
         return res
     planner.plan = plan
     return rows
+
+
+def random_sampling_trials(n: int = 120, seed: int = 11):
+    """Random sampling configurations, initial states and levels (the draws of
+    tests/test_planner_dropin.py::test_candidate_order_matches_reference_sampling_on_random_configurations; the reference's candidate
+    order on them: tests/golden/reference_runs/sampling_order.npz, written by tests/golden/make_reference_runs.py).  Yields per trial
+    a namespace with trial, cfg, ours (this build's FixedIntervalSampling on cfg), level, low_vel, stopping, x0_lon, x0_lat and pick
+    (x0_lat[0] is a lateral sample of the level)."""
+    from types import SimpleNamespace as NS
+    from commonroad_rp_amd.sampling import FixedIntervalSampling
+    rng = np.random.default_rng(seed)
+    for trial in range(n):
+        dt = float(rng.choice([0.1, 0.2]))
+        N = int(rng.integers(10, 41))
+        stopping = trial % 4 == 3
+        levels = int(rng.integers(2, 5))
+        d_min, d_max = -float(rng.choice([1.0, 1.5, 2.0, 3.0])), float(rng.choice([1.0, 2.0, 2.5, 3.0]))
+        t_min = float(dt * int(rng.integers(2, max(3, N // 3))))
+        cfg = NS(planning=NS(dt=dt, time_steps_computation=N),
+                 sampling=NS(sampling_method=1, longitudinal_mode="stopping" if stopping else "velocity_keeping", num_sampling_levels=levels,
+                             t_min=t_min, v_min=float(rng.uniform(0, 4)), v_max=float(rng.uniform(6, 20)), s_min=-float(rng.uniform(1, 8)),
+                             s_max=float(rng.uniform(1, 8)), d_min=d_min, d_max=d_max))
+        ours = FixedIntervalSampling(cfg)
+        level = int(rng.integers(0, levels))
+        low_vel = bool(trial % 5 == 0)
+        x0_lon = [float(rng.uniform(0, 3)), float(rng.uniform(0.5, 3.0) if low_vel else rng.uniform(5, 15)), float(rng.normal(0, 0.3))]
+        d_samples = sorted(ours.samples_d.samples_at_level(level))
+        pick = trial % 3 == 0
+        x0_lat = [float(d_samples[int(rng.integers(0, len(d_samples)))]) if pick else float(rng.uniform(d_min, d_max)), float(rng.normal(0, 0.1)), 0.0]
+        yield NS(trial=trial, cfg=cfg, ours=ours, level=level, low_vel=low_vel, stopping=stopping, x0_lon=x0_lon, x0_lat=x0_lat, pick=pick)
+
+
+def random_plan_cases(n: int = 30, seed0: int = 7000):
+    """Names of the reference's plan() runs on draws of make_golden.random_cases (tests/golden/reference_runs/random_plan_<seed>_<k>.npz,
+    written by tests/golden/make_reference_runs.py)"""
+    return [f"random_plan_{seed0}_{k:02d}" for k in range(n)]
+
+
+REFERENCE_RUNS_DIR = os.path.join(GOLDEN_DIR, "reference_runs")

@@ -108,3 +108,71 @@ def test_committed_round_records_belong_to_the_committed_library():
     assert rf["traffic"] is not None and rf["traffic"] >= rf["bytes_per_launch"]          # (counters of THIS library: else bench.py reports null)
     assert r["value"] == pytest.approx(r["config"]["candidates_per_step"] / (r["ms_per_step"] * 1e-3), rel=1e-3)
     assert rf["kernel_ms"] < r["ms_per_step"]
+
+
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "timing", "roofline", "headline_definition")   # what run_single records without --full
+
+
+def test_plain_line_has_the_headline_only_and_writes_no_detail_file(tmp_path, monkeypatch):
+    """a plain N = 1 run (no --full): the contract's keys and the roofline, nothing of the side records, no detail file"""
+    full = _full_n1()
+    plain = {k: full[k] for k in PLAIN_KEYS if k in full}
+    monkeypatch.setattr(bench, "REPO", str(tmp_path))
+    line = bench.bench_line(plain, types.SimpleNamespace(full=False))
+    r = json.loads(line)
+    for k in CONTRACT:
+        assert k in r, k
+    for k in ("detail", "cpu_baseline", "plan_latency_ms", "side_configs", "production_mode"):
+        assert k not in r, k
+    assert r["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-4) and r["value"] == pytest.approx(full["value"], rel=1e-4)
+    assert os.listdir(str(tmp_path)) == []
+    # --full: the same record through emit, detail file written and named
+    r = json.loads(bench.bench_line(full, types.SimpleNamespace(full=True)))
+    assert os.path.exists(os.path.join(str(tmp_path), r["detail"])) and "cpu_baseline" in r
+
+
+@pytest.mark.parametrize("name", ["arc_hv_l1_draw", "cfg2_ref_draw", "arc_all_collide"])
+def test_dump_outputs(tmp_path, name):
+    """--dump-outputs on the oracle-backed context (the same ctx methods the device context has): float64 files, every value finite,
+    well below 64 MB, the same files from the same plan twice, and contents that are what the context hands its caller"""
+    import numpy as np
+    from _golden import Golden
+    from _oracle_ctx import OracleContext
+    g = Golden(name)
+    ctx = OracleContext(0)
+    g.setup_context(ctx)
+    out = ctx.plan(g.inputs)
+    mode = "draw" if g.draw else "fused"
+    bench.dump_outputs(str(tmp_path / "a"), ctx, out, mode)
+    bench.dump_outputs(str(tmp_path / "b"), ctx, out, mode)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    want = {"best_index", "counts", "reason_counts", "status", "cost", "cost_index"}
+    if out.best_index >= 0:
+        want |= {"best_cost", "best_coeffs", "best_states"}
+    if mode == "draw":
+        want |= {"states_sample", "states_sample_index"}
+    assert {f[:-4] for f in files} == want and all(f.endswith(".npy") for f in files)
+    d, total = {}, 0
+    for f in files:
+        a = np.load(str(tmp_path / "a" / f))
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)), f
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / f))), f
+        d[f[:-4]] = a
+        total += a.nbytes
+    assert total < 64 << 20
+    C = out.n_candidates
+    status, cost = ctx.fetch_status()
+    assert int(d["best_index"][0]) == out.best_index and int(d["counts"][0]) == C
+    np.testing.assert_array_equal(d["status"], status)
+    has = np.isfinite(cost)
+    np.testing.assert_array_equal(d["cost_index"], np.flatnonzero(has))
+    np.testing.assert_array_equal(d["cost"], cost[has])
+    if out.best_index >= 0:
+        assert d["best_cost"][0] == out.best_cost
+        np.testing.assert_array_equal(d["best_states"], out.best_states)
+    if mode == "draw":
+        idx = d["states_sample_index"].astype(np.int64)
+        assert len(idx) == min(C, bench.DUMP_STATE_SAMPLE) and np.all(np.diff(idx) > 0)
+        for i, row in zip(idx[:8], d["states_sample"][:8]):
+            np.testing.assert_array_equal(row, ctx.fetch_states(int(i), 1)[0])

@@ -1,18 +1,14 @@
 """Closed-loop driver (commonroad_rp_amd.harness.run_closed_loop, the loop of run_planner.py:61-107):
-the stand-alone planner and -- where the reference is mounted -- the reference planner itself must trace
-the same state sequence over several replanning cycles (winner hand-over ``optimal[k][1 + temp]``,
-re-sampling of the velocity grid from the current speed, table re-use across ``reset``)."""
+the stand-alone planner and the reference planner itself (its trace recorded in tests/golden/reference_runs/closed_loop.npz by
+tests/golden/make_reference_runs.py) must trace the same state sequence over several replanning cycles (winner hand-over
+``optimal[k][1 + temp]``, re-sampling of the velocity grid from the current speed, table re-use across ``reset``)."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from _golden import build_planner_from_plan_golden
+from _golden import REFERENCE_RUNS_DIR, build_planner_from_plan_golden
 from commonroad_rp_amd.harness import run_closed_loop
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-HAVE_REF = os.path.isdir("/root/reference/commonroad_rp")
 
 
 def _trace(states):
@@ -28,16 +24,8 @@ def test_closed_loop_cpu_glue_matches_reference(name):
     assert res.completed and res.n_replans == 4 and len(res.states) == 13
     tr = _trace(res.states)
     assert np.all(np.diff(tr[:, 0]) == 1)            # consecutive time steps
-    if not HAVE_REF:
-        return
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_golden as mg
-    case = {c["name"]: c for c in mg.plan_cases()}[name]
-    ref = mg.make_planner(dict(case))
-    ref.record_state_and_input = lambda state: ref._record_state_list.append(state)   # InputState is a stand-in here
-    ref_res = run_closed_loop(ref, max_steps=12, desired_velocity=float(z["desired_speed"]))
-    assert ref_res.completed
-    np.testing.assert_allclose(tr, _trace(ref_res.states), rtol=0, atol=1e-8)
+    ref = np.load(os.path.join(REFERENCE_RUNS_DIR, "closed_loop.npz"))[name]
+    np.testing.assert_allclose(tr, ref, rtol=0, atol=1e-8)
 
 
 @pytest.mark.gpu

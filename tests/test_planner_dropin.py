@@ -1,134 +1,14 @@
-"""Drop-in check against the REAL reference class: ``GpuBackendMixin`` mixed into
-``commonroad_rp.reactive_planner.ReactivePlanner`` (imported read-only from /root/reference under the
-third-party stand-ins of tests/golden/_ref_shims.py), with everything else of the reference -- plan(),
-its own FixedIntervalSampling / DefaultCostFunction objects, _compute_trajectory_pair -- untouched.
-Compared with the unmodified reference planner on the same inputs.
-
-Only runs where the reference is mounted (the build container); skipped on the GPU box.
-The mixin's backend here is the oracle-backed context (CPU).  Two plug-in paths are exercised:
-  * the reference's FixedIntervalSampling has no ``grids_at_level`` -> "foreign sampling space" path
-    (explicit polynomials, rp_plan_coeffs);
-  * a user CostFunction subclass -> plug-in cost path (materialise, evaluate in Python, rp_select).
+"""This build's planner against the REFERENCE's own behaviour, recorded in tests/golden/reference_runs/ by
+tests/golden/make_reference_runs.py (which runs the unmodified reference under the third-party stand-ins of
+tests/golden/_ref_shims.py): the candidate order of the reference's sampling on random configurations, and whole plan() cycles on
+random cases.  The planner's backend here is the oracle-backed context (CPU).
 """
 import os
-import sys
 
 import numpy as np
-import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if not os.path.isdir("/root/reference/commonroad_rp"):
-    pytest.skip("reference not mounted", allow_module_level=True)
-
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_golden as mg  # noqa: E402  (installs the stand-ins and imports the reference)
-
-from commonroad_rp.reactive_planner import ReactivePlanner as RefPlanner  # noqa: E402
-from commonroad_rp.cost_function import DefaultCostFunction as RefDefaultCost  # noqa: E402
-from commonroad_rp_amd.reactive_planner import GpuBackendMixin  # noqa: E402
-from _oracle_ctx import OracleContext  # noqa: E402
-from _golden import scenario_from_tables  # noqa: E402
-
-
-class DropInPlanner(GpuBackendMixin, RefPlanner):
-    backend_factory = OracleContext
-
-
-def _planner(case, cls):
-    rp = mg.make_planner(dict(case))
-    if cls is not RefPlanner:
-        rp.__class__ = cls       # same attributes, methods of the mixin in front of the reference's
-        if case.get("via_scenario"):
-            # the reference's own entry: its (stand-in) pycrcc checker is rebuilt from the scenario by the parent class,
-            # the mixin extracts the tables of the GPU check from the same scenario -- including the OBB sums of the
-            # dynamic obstacles when planning.continuous_collision_check is on (reactive_planner.py:238-245)
-            sc = scenario_from_tables(case["obstacles"])
-            rp.set_collision_checker(scenario=sc, road_boundary_obstacle=sc.road_boundary_triangles)
-        else:
-            rp.set_obstacle_tables(case.get("obstacles"))
-    return rp
-
-
-def _states(res):
-    cart, cvln, lon_list, lat_list = res
-    c = np.array([[s.time_step, s.position[0], s.position[1], s.orientation, s.velocity, s.acceleration, s.yaw_rate,
-                   s.steering_angle] for s in cart.state_list], dtype=float)
-    return c, np.array(lon_list, dtype=float), np.array(lat_list, dtype=float)
-
-
-CASES = {c["name"]: c for c in mg.plan_cases()}
-
-
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_mixin_on_reference_class_matches_reference(name):
-    ref = _planner(CASES[name], RefPlanner)
-    gpu = _planner(CASES[name], DropInPlanner)
-    r0, r1 = ref.plan(), gpu.plan()
-    assert (r0 is None) == (r1 is None)
-    assert gpu.infeasible_count_kinematics == ref.infeasible_count_kinematics
-    assert gpu.infeasible_count_collision == ref.infeasible_count_collision
-    assert gpu.infeasible_reason_dict == ref.infeasible_reason_dict
-    if r0 is not None:
-        for a, b in zip(_states(r0), _states(r1)):
-            np.testing.assert_allclose(b, a, rtol=0, atol=1e-9)
-
-
-class BiasedCost(RefDefaultCost):
-    """user plug-in: default cost plus a penalty on driving left of the reference path"""
-
-    def evaluate(self, trajectory):
-        return super().evaluate(trajectory) + 40.0 * float(np.sum(np.maximum(trajectory.curvilinear.d, 0.0)))
-
-
-def test_plugin_cost_function_path():
-    case = CASES["plan_arc_hv_obs"]
-    ref, gpu = _planner(case, RefPlanner), _planner(case, DropInPlanner)
-    for p in (ref, gpu):
-        cf = BiasedCost(p.cost_function.desired_speed, desired_d=0.0, desired_s=None)
-        p.set_cost_function(cf)
-    r0, r1 = ref.plan(), gpu.plan()
-    assert r0 is not None and r1 is not None
-    for a, b in zip(_states(r0), _states(r1)):
-        np.testing.assert_allclose(b, a, rtol=0, atol=1e-9)
-    assert gpu.infeasible_count_collision == ref.infeasible_count_collision
-
-
-def test_draw_traj_set_stores_every_trajectory():
-    case = dict(CASES["plan_arc_hv_obs"], draw=True)
-    ref, gpu = _planner(case, RefPlanner), _planner(case, DropInPlanner)
-    ref.plan(), gpu.plan()
-    assert len(gpu.stored_trajectories) == len(ref.stored_trajectories)
-    key = lambda t: (t.trajectory_long.delta_tau, t.trajectory_long.x_d[0], t.trajectory_lat.x_d[0])   # noqa: E731
-    mine = {key(t): t for t in gpu.stored_trajectories}
-    for t in ref.stored_trajectories:
-        m = mine[key(t)]
-        np.testing.assert_allclose(m.cartesian.x, t.cartesian.x, rtol=0, atol=1e-9)
-        np.testing.assert_allclose(m.cartesian.kappa_dot, t.cartesian.kappa_dot, rtol=0, atol=1e-9)
-        np.testing.assert_allclose(m.curvilinear.s, t.curvilinear.s, rtol=0, atol=1e-9)
-        kin_ref = t.feasibility_label is not None and t.feasibility_label.value == "infeasible_kinematic"
-        kin_me = m.feasibility_label is not None and m.feasibility_label.value == "infeasible_kinematic"
-        assert kin_ref == kin_me
-
-
-def test_opaque_collision_checker_is_refused_not_ignored():
-    """set_collision_checker(collision_checker=<pycrcc checker>) -- what reset(collision_checker=...) triggers -- must
-    not leave the GPU path with stale or empty tables: the checker the tables were extracted for passes, a foreign one
-    raises, and a planner left in that state refuses to plan."""
-    case = CASES["plan_arc_cross_obbsum"]
-    gpu = _planner(case, DropInPlanner)
-    tables = gpu._obstacle_tables
-    gpu.reset(initial_state_cart=gpu.x_0, initial_state_curv=gpu.x_0_cl, collision_checker=gpu._cc, coordinate_system=gpu._co)
-    assert gpu._obstacle_tables is tables            # same checker handed back (run_planner.py:99-107): tables kept
-    foreign = mg._ref_shims.CollisionChecker(case["obstacles"])
-    with pytest.raises(TypeError, match="cannot read the content"):
-        gpu.set_collision_checker(collision_checker=foreign)
-    with pytest.raises(TypeError, match="refusing to plan"):
-        gpu.plan()
-    foreign.obstacle_tables = tables                 # documented way to use a ready-made checker
-    gpu.set_collision_checker(collision_checker=foreign)
-    assert gpu.plan() is not None
-    with pytest.raises(TypeError, match="road_boundary_obstacle"):
-        gpu.set_collision_checker(scenario=scenario_from_tables(case["obstacles"]), road_boundary_obstacle=object())
+from _golden import REFERENCE_RUNS_DIR, random_plan_cases, random_sampling_trials
+from _oracle_ctx import OracleContext
 
 
 def test_candidate_order_matches_reference_sampling_on_random_configurations():
@@ -136,38 +16,15 @@ def test_candidate_order_matches_reference_sampling_on_random_configurations():
     REFERENCE's ``generate_trajectories_at_level`` (sampling.py:202-242) on random sampling configurations: the (T, lon, d) sequence of
     the reference's candidate list must be the product order of the grids -- including vehicles that sit exactly on a lateral sample
     (the union is then a copy of the set, whose iteration order may differ from the set's own), stopping mode with goals behind the
-    vehicle, and both velocity regimes."""
-    from types import SimpleNamespace as NS
-    from commonroad_rp.sampling import FixedIntervalSampling as RefSampling
-    from commonroad_rp_amd.sampling import FixedIntervalSampling as OurSampling
+    vehicle, and both velocity regimes.  The reference's candidate lists: tests/golden/reference_runs/sampling_order.npz."""
     from commonroad_rp_amd import _capi
-    rng = np.random.default_rng(11)
+    orders = np.load(os.path.join(REFERENCE_RUNS_DIR, "sampling_order.npz"))
     checked = on_sample = 0
-    for trial in range(120):
-        dt = float(rng.choice([0.1, 0.2]))
-        N = int(rng.integers(10, 41))
-        stopping = trial % 4 == 3
-        levels = int(rng.integers(2, 5))
-        d_min, d_max = -float(rng.choice([1.0, 1.5, 2.0, 3.0])), float(rng.choice([1.0, 2.0, 2.5, 3.0]))
-        t_min = float(dt * int(rng.integers(2, max(3, N // 3))))
-        cfg = NS(planning=NS(dt=dt, time_steps_computation=N),
-                 sampling=NS(sampling_method=1, longitudinal_mode="stopping" if stopping else "velocity_keeping", num_sampling_levels=levels,
-                             t_min=t_min, v_min=float(rng.uniform(0, 4)), v_max=float(rng.uniform(6, 20)), s_min=-float(rng.uniform(1, 8)),
-                             s_max=float(rng.uniform(1, 8)), d_min=d_min, d_max=d_max))
-        ref, ours = RefSampling(cfg), OurSampling(cfg)
-        level = int(rng.integers(0, levels))
-        low_vel = bool(trial % 5 == 0)
-        x0_lon = [float(rng.uniform(0, 3)), float(rng.uniform(0.5, 3.0) if low_vel else rng.uniform(5, 15)), float(rng.normal(0, 0.3))]
-        d_samples = sorted(ours.samples_d.samples_at_level(level))
-        pick = trial % 3 == 0
-        x0_lat = [float(d_samples[int(rng.integers(0, len(d_samples)))]) if pick else float(rng.uniform(d_min, d_max)), float(rng.normal(0, 0.1)), 0.0]
+    for tr in random_sampling_trials():
+        trial, ours, level, x0_lon, x0_lat, pick = tr.trial, tr.ours, tr.level, tr.x0_lon, tr.x0_lat, tr.pick
         on_sample += pick
-        mode = cfg.sampling.longitudinal_mode
-        cand = ref.generate_trajectories_at_level(level, x0_lon, x0_lat, mode, low_vel)
-        if stopping:   # what _get_optimal_trajectory does to the list first (reactive_planner.py:1076-1077, trajectories.py:545-550)
-            cand = [c for c in cand if c.trajectory_long.x_d[0] > x0_lon[0]]
-        got = np.array([[c.trajectory_long.delta_tau, c.trajectory_long.x_d[0] if stopping else c.trajectory_long.x_d[0], c.trajectory_lat.x_d[0]] for c in cand],
-                       dtype=float).reshape(-1, 3)
+        mode = tr.cfg.sampling.longitudinal_mode
+        got = orders[f"t{trial}"]   # (stopping: the list as _get_optimal_trajectory filters it first, reactive_planner.py:1076-1077)
         T, tl, L, D = ours.grids_at_level(level, x0_lon, x0_lat, mode)
         want = np.array([[t, l, d] for t in T for l in L for d in D], dtype=float).reshape(-1, 3)
         # (velocity keeping: a quartic's end condition is x_d = [v, 0]; stopping: a quintic's [s, 0, 0] -- the first entry either way;
@@ -190,110 +47,17 @@ def test_candidate_order_matches_reference_sampling_on_random_configurations():
 
 
 def test_own_planner_matches_live_reference_plan_on_random_cases():
-    """This build's ``ReactivePlanner`` (oracle-backed context: host logic + restated arithmetic) against the reference's ``plan()`` run
-    HERE on further draws of make_golden.random_cases -- whole cycles: level loop, counters, output packing -- a third of them with the
-    vehicle exactly on a lateral sample of the level (candidate order = iteration order of a COPY of the sample set)."""
+    """This build's ``ReactivePlanner`` (oracle-backed context: host logic + restated arithmetic) against the reference's ``plan()`` on
+    further draws of make_golden.random_cases (its runs: tests/golden/reference_runs/random_plan_*.npz, make_reference_runs.py) -- whole
+    cycles: level loop, counters, output packing -- a third of them with the vehicle exactly on a lateral sample of the level
+    (candidate order = iteration order of a COPY of the sample set)."""
     from _golden import build_planner_from_plan_golden, compare_plan_result
     done = planned = 0
-    for k, case in enumerate(mg.random_cases(n=30, seed0=7000)):
-        case = dict(case, draw=False, cost_kind=0)
-        case.pop("constraints", None)
-        case.pop("level", None)
-        if k % 3 == 0:   # on a sample of the first level plan() visits (level 1: 5 samples of [-3, 3]; three of them also at level 2 / 3)
-            case["x0_lat"] = [float(np.linspace(-3, 3, 5)[1 + k % 3 + (k // 3) % 2]), case["x0_lat"][1], case["x0_lat"][2]]
-        out = mg.run_plan_case(dict(case))
+    for name in random_plan_cases(n=30, seed0=7000):
+        out = dict(np.load(os.path.join(REFERENCE_RUNS_DIR, name + ".npz")))
         rp, z = build_planner_from_plan_golden(out, OracleContext)
         res = rp.plan()
         compare_plan_result(res, rp, z, atol=1e-9)
         done += 1
         planned += res is not None
     assert done == 30 and planned >= 10
-
-
-def test_mixin_on_reference_class_matches_reference_on_random_cases():
-    """the drop-in construction (GpuBackendMixin in front of the REAL reference class, its own sampling space and cost function: the
-    'foreign sampling space' path, explicit polynomials) against the unmodified reference on further draws of make_golden.random_cases"""
-    done = planned = 0
-    for k, case in enumerate(mg.random_cases(n=24, seed0=8000)):
-        case = dict(case, draw=False)
-        case.pop("level", None)
-        if k % 3 == 0:
-            case["x0_lat"] = [float(np.linspace(-3, 3, 5)[1 + (k // 3) % 3]), case["x0_lat"][1], case["x0_lat"][2]]
-        ref = _planner(case, RefPlanner)
-        gpu = _planner(case, DropInPlanner)
-        try:
-            r0 = ref.plan()
-        except ValueError:   # (the reference gives up on some made-up configurations: a time sample one step beyond the horizon)
-            continue
-        r1 = gpu.plan()
-        assert (r0 is None) == (r1 is None), case["name"]
-        assert gpu.infeasible_count_kinematics == ref.infeasible_count_kinematics, case["name"]
-        assert gpu.infeasible_count_collision == ref.infeasible_count_collision, case["name"]
-        assert gpu.infeasible_reason_dict == ref.infeasible_reason_dict, case["name"]
-        if r0 is not None:
-            for a, b in zip(_states(r0), _states(r1)):
-                np.testing.assert_allclose(b, a, rtol=0, atol=1e-9, err_msg=case["name"])
-        done += 1
-        planned += r0 is not None
-    assert done >= 20 and planned >= 8
-
-
-def test_setters_leave_the_same_sampling_sets_and_cost_parameters_as_the_reference():
-    """random sequences of the planner's setters (reactive_planner.py:274-376: time / lateral / velocity / position sampling, desired
-    velocity with and without the current speed and the stopping flag, desired longitudinal position with and without its deltas) on the
-    reference's planner and on this build's: the same sample sets at every level afterwards -- as SETS and in iteration order --, the
-    same desired speed / position and the same cost-function parameters"""
-    from _golden import build_planner_from_plan_golden
-    base = CASES["plan_arc_hv_obs"]
-    ref = _planner(base, RefPlanner)
-    out = mg.run_plan_case(dict(base))
-    ours, _ = build_planner_from_plan_golden(out, OracleContext)
-    rng = np.random.default_rng(21)
-
-    def same():
-        for kind in ("samples_t", "samples_d", "samples_v", "samples_s"):
-            a, b = getattr(ref.sampling_space, kind), getattr(ours.sampling_space, kind)
-            if a is None or b is None:
-                assert a is None and b is None, kind
-                continue
-            for level in range(ref.sampling_level):
-                sa, sb = a.samples_at_level(level), b.samples_at_level(level)
-                assert list(sa) == list(sb), (kind, level)
-        assert ref._desired_speed == ours._desired_speed and ref._desired_lon_position == ours._desired_lon_position
-        for k in ("desired_speed", "w_a", "desired_s", "desired_d"):
-            assert getattr(ref.cost_function, k) == getattr(ours.cost_function, k), k
-    same()
-    for step in range(300):
-        op = int(rng.integers(0, 7))
-        if op == 0:
-            a = (float(0.1 * int(rng.integers(2, 12))),)
-            name = "set_t_sampling_parameters"
-        elif op == 1:
-            lo = -float(rng.uniform(0.2, 4)); a = (lo, float(rng.uniform(0.2, 4)))
-            name = "set_d_sampling_parameters"
-        elif op == 2:
-            lo = float(rng.uniform(0, 10)); a = (lo, lo + float(rng.uniform(0, 12)))
-            name = "set_v_sampling_parameters"
-        elif op == 3:
-            lo = float(rng.uniform(-5, 30)); a = (lo, lo + float(rng.uniform(0.1, 12)))
-            name = "set_s_sampling_parameters"
-        elif op == 4:
-            name = "set_desired_velocity"
-            kw = {}
-            if rng.random() < 0.7:
-                kw["desired_velocity"] = float(rng.uniform(0, 20))
-            if rng.random() < 0.6:
-                kw["current_speed"] = float(rng.uniform(0, 20))
-            if rng.random() < 0.2:
-                kw["stopping"] = True
-            getattr(ref, name)(**kw); getattr(ours, name)(**kw)
-            same()
-            continue
-        elif op == 5:
-            name = "set_desired_lon_position"
-            a = (float(rng.uniform(5, 80)),) + ((-float(rng.uniform(0, 8)), float(rng.uniform(0, 8))) if rng.random() < 0.5 else ())
-        else:
-            name = "set_desired_velocity"
-            a = ()
-        getattr(ref, name)(*a); getattr(ours, name)(*a)
-        same()
