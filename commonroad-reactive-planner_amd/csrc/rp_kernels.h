@@ -23,15 +23,6 @@
     __builtin_nontemporal_store(*reinterpret_cast<const __attribute__((ext_vector_type(2))) double *>(&(v)),        \
                                 reinterpret_cast<__attribute__((ext_vector_type(2))) double *>(p))
 #endif
-#ifndef RP_WRITE_THROUGH
-#ifndef RP_BRANCHFREE_CONSTRAINTS
-#define RP_BRANCHFREE_CONSTRAINTS 1
-#endif
-#define RP_WRITE_THROUGH 1   // single-launch variant: agent-scope write-through stores of the state rows (see st_row)
-#endif
-#ifndef RP_LATE_KERNARGS
-#define RP_LATE_KERNARGS 1   // single-launch variant: kernel arguments of the step loop are loaded after the prologue
-#endif
 #ifndef RP_WAVES_PER_SIMD
 #define RP_WAVES_PER_SIMD 3  // register budget of the evaluation kernel: 512 / 3 -> 168 VGPRs.  One wavefront issues
                              // an instruction only every ~10-13 cycles (profiles/r01_instruction_costs.txt), so the
@@ -1105,6 +1096,118 @@ __device__ __forceinline__ double frenet_acc(double sdd, double f, double sd, do
     return __builtin_fma(sdd, f, (sd * sd * secT) * __builtin_fma(oneKrD * tanT, __builtin_fma(kappa, f, -k_r), -kterm));
 }
 
+// ---- One step of a candidate, shared by the three kernels that judge candidates (rp_eval_kernel, rp_cost_kernel, rp_chunk_kernel):
+// they must agree bit for bit on labels, reasons, first failing steps and costs.  The helpers that read kernel arguments take them as
+// a template type, so that rp_eval_kernel's kernarg-segment reference (late loads, see there) binds as well as a plain `const KArgs &`.
+
+// this lane's share of the cost of one (possibly extended) state, cost_function.py:51-71 / 82-92: every step adds its own terms, steps
+// N and N/2 (mid = int(len(v) / 2), cost_function.py:59) also the terminal ones
+template <class KA>
+__device__ __forceinline__ double cost_terms(const KA &a, int i, int N, int mid, double acc, double v, double s, double d, double th_cl) {
+    double e, cst;
+    e = a.w_a * acc; cst = e * e;
+    e = 0.25 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
+    e = 0.25 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
+    if (a.has_speed) { e = 5.0 * (v - a.desired_speed); cst = __builtin_fma(e, e, cst); }
+    if (a.has_s) { e = 0.25 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
+    if (i == N) {
+        e = 20.0 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
+        e = 5.0 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
+        if (a.has_speed) { e = v - a.desired_speed; cst += 50.0 * (e * e); }
+        if (a.has_s) { e = 20.0 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
+    }
+    if (i == mid && a.has_speed) { e = v - a.desired_speed; cst += 100.0 * (e * e); }
+    return cst;
+}
+
+// _check_constraints, reactive_planner.py:971-1017: the first failing test in the reference's order (velocity, kappa, yaw, kappa_dot,
+// acc) or RP_REASON_NONE.  Straight-line code: every lane evaluates the five tests and selects pick the reason -- as an if / else-if
+// chain the compiler emitted five nested exec-mask regions, each with its own scalar loads of the limits and a wait on them.
+template <class KA>
+__device__ __forceinline__ uint32_t constraint_reason(const KA &a, uint32_t cm, double v, double acc, double kappa, double dth, double kdot) {
+    uint32_t reason = RP_REASON_NONE;
+    const double a_max = a.a_max, v_switch = a.v_switch, kappa_max = a.kappa_max;
+    const double wk = a.wheelbase * kappa;
+    // |round(yaw, 5)| > kappa_max v           with yaw = dth / dt           (:993-995)
+    const bool bad_yaw = fabs(rint(dth * a.c_yaw)) > kappa_max * v * 1e5;
+    // |dka / dt| > v_delta_max / (wb cos^2(atan(wb kappa)))                  (:1001-1005)
+    const bool bad_kd = fabs(kdot) > a.c_kdot * __builtin_fma(wk, wk, 1.0);
+    // a_min <= a <= a_max (v_switch / v above the switching velocity)        (:1011-1014)
+    const bool fast = v > v_switch;
+    const double acc_l = fast ? acc * v : acc, acc_r = fast ? a_max * v_switch : a_max;
+    const bool bad_acc = !((-a_max <= acc) & (acc_l <= acc_r));
+    const bool bad_v = v < -RP_EPS, bad_k = fabs(kappa) > kappa_max;
+    reason = (((cm & RP_CHECK_ACCELERATION) != 0) & bad_acc) ? RP_REASON_ACCELERATION : reason;
+    reason = (((cm & RP_CHECK_KAPPA_DOT) != 0) & bad_kd) ? RP_REASON_KAPPA_DOT : reason;
+    reason = (((cm & RP_CHECK_YAW_RATE) != 0) & bad_yaw) ? RP_REASON_YAW_RATE : reason;
+    reason = (((cm & RP_CHECK_KAPPA) != 0) & bad_k) ? RP_REASON_KAPPA : reason;
+    reason = (((cm & RP_CHECK_VELOCITY) != 0) & bad_v) ? RP_REASON_VELOCITY : reason;
+    return reason;
+}
+
+// d', d'' from the lateral polynomial's d_dot, d_ddot (reactive_planner.py:810-832)
+__device__ __forceinline__ void lateral_derivs(bool low, double dd, double ddd, double inv_sd, double sdd, double &dp, double &dpp) {
+    if (!low) {
+        dp = dd * inv_sd;
+        const double ddot = ddd - dp * sdd;
+        dpp = ddot * inv_sd * inv_sd;
+    } else {
+        dp = dd;
+        dpp = ddd;
+    }
+}
+
+// orientations on the atan branch (reactive_planner.py:842-873): theta_cl = np.arctan2(dp, 1.0), theta_gl, and cos / sec / tan of
+// theta_cl, algebraic
+__device__ __forceinline__ void atan_angles(double dp, double th_ref, double &th_cl, double &th_gl, double &cosT, double &secT, double &tanT) {
+    th_cl = rp_atan(dp);
+    th_gl = th_cl + th_ref;
+    const double w2 = __builtin_fma(dp, dp, 1.0);
+    cosT = rp_rsqrt(w2);
+    secT = w2 * cosT;
+    tanT = dp;
+}
+
+// cos / sec / tan of theta_cl for the standstill lanes (!use_atan), once their th_cl holds the carried orientation (:866)
+__device__ __forceinline__ void standstill_angles(double th_cl, bool use_atan, double &cosT, double &secT, double &tanT) {
+    double sn, cs;
+    rp_sincos(th_cl, &sn, &cs);
+    const double sc = rp_rcp(cs);
+    cosT = use_atan ? cosT : cs;
+    secT = use_atan ? secT : sc;
+    tanT = use_atan ? tanT : sn * sc;
+}
+
+// curvature, velocity, acceleration (reactive_planner.py:883-896)
+__device__ __forceinline__ void frenet_kinematics(double d, double dp, double dpp, double sd, double sdd, double k_r, double k_r_d,
+                                                  double cosT, double secT, double tanT, double &kappa, double &v, double &acc) {
+    const double oneKrD = 1.0 - k_r * d;
+    const double q = cosT * rp_rcp(oneKrD);
+    const double kterm = frenet_kterm(k_r_d, d, k_r, dp);
+    kappa = frenet_kappa(dpp, kterm, tanT, cosT, q, k_r);
+    const double f = oneKrD * secT;
+    v = sd * f;
+    acc = frenet_acc(sdd, f, sd, secT, oneKrD, tanT, kappa, k_r, kterm);
+}
+
+// horizon extension (trajectories.py:168-197, 302-332) from the last valid state, tk = (i - L + 1) dt (np.arange(1, steps + 1) * dt)
+__device__ __forceinline__ void extended_state(double l_v, double l_acc, double l_s, double l_sd, double l_d, double l_dd, double tk,
+                                               double &vt, double &e_s, double &e_d) {
+    vt = l_v + tk * l_acc;                 // :182 (a[-1] already holds a[last])
+    vt = vt * (vt >= 0.0 ? 1.0 : 0.0);     // :184
+    e_s = l_s + tk * l_sd;                 // :330
+    e_d = l_d + tk * l_dd;                 // :331
+}
+
+// first pass of the two-kernel path: workgroup 0 clears the control block of the lazy stage and seeds the bound of the bounded sweep
+// (no free candidate known yet)
+__device__ __forceinline__ void clear_pass1_controls(const KArgs &a, int tid) {
+    if (a.lazy_ctl && blockIdx.x == 0 && tid < (int)(sizeof(LazyCtl) / 8))
+        reinterpret_cast<unsigned long long *>(a.lazy_ctl)[tid] = 0ull;
+    if (a.sweep_init && blockIdx.x == 0 && tid == 0)
+        __hip_atomic_store(a.sweep_init, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Per-group LDS scratch of the evaluation kernel.  Values that are identical in all lanes of a group
 // and live for the whole candidate are parked here and re-read (broadcast reads) where they are used.
 //   poly[0..14]  lateral polynomial: c0..c5 | c1, 2c2, 3c3, 4c4, 5c5 | 2c2, 6c3, 12c4, 20c5
@@ -1702,7 +1805,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
     const KArgs &a = ag.k;
     extern __shared__ double lds_out[];   // STAGE_OUT: [groups per block][14][N+1];  LON_FUSED: tables, profiles, headers, votes
     static_assert(!(LON_FUSED && STAGE_OUT), "the single-launch variant stores state rows directly");
-    constexpr bool RP_WT = LON_FUSED && RP_WRITE_THROUGH;
+    constexpr bool RP_WT = LON_FUSED;   // single-launch variant: agent-scope write-through stores of the state rows (see st_row)
     constexpr bool RP_NT = MAT && !LON_FUSED && !STAGE_OUT;   // rows of the two-kernel path stored straight to memory: streaming stores
     touch_kernargs<10>();
 
@@ -1742,10 +1845,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
         }
     }
     const int64_t count = count_;
-    if (!LON_FUSED && a.lazy_ctl && blockIdx.x == 0 && tid < (int)(sizeof(LazyCtl) / 8))   // (first pass of the lazy stage)
-        reinterpret_cast<unsigned long long *>(a.lazy_ctl)[tid] = 0ull;
-    if (!LON_FUSED && a.sweep_init && blockIdx.x == 0 && tid == 0)   // (pass 1 of the bounded sweep: no free candidate known yet)
-        __hip_atomic_store(a.sweep_init, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!LON_FUSED) clear_pass1_controls(a, tid);
     // The sweep itself: a lane group evaluates its candidate only if pass 1 left it FEASIBLE and no cheaper free candidate is known; a
     // workgroup none of whose candidates needs that leaves an empty partial and is gone after one round trip.
     constexpr bool sweep = SWEEP;
@@ -2061,7 +2161,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
     // Variants that write no state rows and have no long prologue keep the plain argument accesses (entry-block loads):
     // they spilled little to begin with and lose 2 % to the later loads (cfg5 production mode 1.126 -> 1.155 ms).
     kargs_cptr ap_late = (LON_FUSED || MAT) ? (kargs_cptr)__builtin_amdgcn_kernarg_segment_ptr() : (kargs_cptr)&a;
-    if (RP_LATE_KERNARGS && LON_FUSED) asm volatile("" : "+s"(ap_late));
+    if (LON_FUSED) asm volatile("" : "+s"(ap_late));
     const KArgs __attribute__((address_space(4))) &al = *ap_late;
     const int N = al.N, n = N + 1;
     const int nchunks = ONE_CHUNK ? 1 : (n + G - 1) / G;
@@ -2073,9 +2173,10 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
     double *const gs_poly = sh_grp[grp].poly;
     double *const gs_last = sh_grp[grp].last;
 
-    // this lane's share of the cost of one (possibly extended) state, cost_function.py:51-71 / 82-92:
-    // every lane adds its own step, the lanes holding steps N and N/2 also add the terminal terms
-    auto cost_terms = [&](int i, double acc, double v, double s, double d, double th_cl) -> double {
+    // this lane's share of the cost of one (possibly extended) state: cost_terms() above, expression for expression.  Kept as a lambda
+    // here: called as the helper, the compiler allocates registers differently in the variants with state rows (up to six VGPRs more
+    // spilled, e.g. rp_eval_kernel<64, MAT, grid, COLL 2, ONE_CHUNK, STAGE_OUT>).
+    auto eval_cost_terms = [&](int i, double acc, double v, double s, double d, double th_cl) -> double {
         double e, cst;
         e = al.w_a * acc; cst = e * e;
         e = 0.25 * (al.desired_d - d); cst = __builtin_fma(e, e, cst);
@@ -2213,24 +2314,12 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     // -- d', d'' (:810-832)
                     const bool moving = inv_sd > 0.0;
                     double dp, dpp;
-                    if (!low) {
-                        dp = dd * inv_sd;
-                        const double ddot = ddd - dp * sdd;
-                        dpp = ddot * inv_sd * inv_sd;
-                    } else {
-                        dp = dd;
-                        dpp = ddd;
-                    }
+                    lateral_derivs(low, dd, ddd, inv_sd, sdd, dp, dpp);
 
                     // -- orientations (:842-873) incl. the standstill carry of :866
                     const bool use_atan = moving || low;
-                    th_cl = rp_atan(dp);          // np.arctan2(dp, 1.0)
-                    th_gl = th_cl + th_ref;
-                    // cos / sec / tan of theta_cl: algebraic on the atan branch
-                    const double w2 = __builtin_fma(dp, dp, 1.0);
-                    double cosT = rp_rsqrt(w2);
-                    double secT = w2 * cosT;
-                    double tanT = dp;
+                    double cosT, secT, tanT;
+                    atan_angles(dp, th_ref, th_cl, th_gl, cosT, secT, tanT);
                     if (__any(act && !use_atan)) {   // standstill lanes: keep the orientation of the last moving step
                         const uint64_t mv = group_ballot<G>(use_atan && act, gbase);
                         const uint64_t below = mv & ((1ull << gl) - 1ull);
@@ -2240,12 +2329,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                             th_gl = below ? th_from : theta_carry;
                             th_cl = th_gl - th_ref;
                         }
-                        double sn, cs;
-                        rp_sincos(th_cl, &sn, &cs);
-                        const double sc = rp_rcp(cs);
-                        cosT = use_atan ? cosT : cs;
-                        secT = use_atan ? secT : sc;
-                        tanT = use_atan ? tanT : sn * sc;
+                        standstill_angles(th_cl, use_atan, cosT, secT, tanT);
                     }
                     // cos / sin of the heading theta = theta_ref + theta_cl from the profile's cos / sin of theta_ref (variants with a
                     // collision query; the others need them for one lane per candidate only, where the extension starts)
@@ -2255,13 +2339,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     RP_STAMP(5);   // atan + carry
 
                     // -- curvature, velocity, acceleration (:883-896)
-                    const double oneKrD = 1.0 - k_r * d;
-                    const double q = cosT * rp_rcp(oneKrD);
-                    const double kterm = frenet_kterm(k_r_d, d, k_r, dp);
-                    kappa = frenet_kappa(dpp, kterm, tanT, cosT, q, k_r);
-                    const double f = oneKrD * secT;
-                    v = sd * f;
-                    acc = frenet_acc(sdd, f, sd, secT, oneKrD, tanT, kappa, k_r, kterm);
+                    frenet_kinematics(d, dp, dpp, sd, sdd, k_r, k_r_d, cosT, secT, tanT, kappa, v, acc);
 
                     // -- previous-step values for the finite differences (DPP lane shift)
                     double th_prev = lane_prev(th_gl), ka_prev = lane_prev(kappa);
@@ -2270,48 +2348,9 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     kdot = i > 0 ? kappa - ka_prev : 0.0;   // np.append([0], np.diff(kappa_gl)), :923
                     RP_STAMP(6);   // kappa, v, a + prev-step shifts
 
-                    // -- _check_constraints, reactive_planner.py:971-1017 (order: velocity, kappa, yaw, kappa_dot, acc)
-    #if RP_BRANCHFREE_CONSTRAINTS
-                    // (straight-line code: every lane evaluates the five tests and the first failing one in the reference's order is
-                    //  picked by selects -- as an if / else-if chain the compiler emitted five nested exec-mask regions, each with its
-                    //  own scalar loads of the limits and a wait on them)
-                    uint32_t reason = RP_REASON_NONE;
-                    {
-                        const double a_max = al.a_max, v_switch = al.v_switch, kappa_max = al.kappa_max;
-                        const double wk = al.wheelbase * kappa;
-                        // |round(yaw, 5)| > kappa_max v           with yaw = dth / dt           (:993-995)
-                        const bool bad_yaw = fabs(rint(dth * al.c_yaw)) > kappa_max * v * 1e5;
-                        // |dka / dt| > v_delta_max / (wb cos^2(atan(wb kappa)))                  (:1001-1005)
-                        const bool bad_kd = fabs(kdot) > al.c_kdot * __builtin_fma(wk, wk, 1.0);
-                        // a_min <= a <= a_max (v_switch / v above the switching velocity)        (:1011-1014)
-                        const bool fast = v > v_switch;
-                        const double acc_l = fast ? acc * v : acc, acc_r = fast ? a_max * v_switch : a_max;
-                        const bool bad_acc = !((-a_max <= acc) & (acc_l <= acc_r));
-                        const bool bad_v = v < -RP_EPS, bad_k = fabs(kappa) > kappa_max;
-                        reason = (((cm & RP_CHECK_ACCELERATION) != 0) & bad_acc) ? RP_REASON_ACCELERATION : reason;
-                        reason = (((cm & RP_CHECK_KAPPA_DOT) != 0) & bad_kd) ? RP_REASON_KAPPA_DOT : reason;
-                        reason = (((cm & RP_CHECK_YAW_RATE) != 0) & bad_yaw) ? RP_REASON_YAW_RATE : reason;
-                        reason = (((cm & RP_CHECK_KAPPA) != 0) & bad_k) ? RP_REASON_KAPPA : reason;
-                        reason = (((cm & RP_CHECK_VELOCITY) != 0) & bad_v) ? RP_REASON_VELOCITY : reason;
-                        reason = act ? reason : RP_REASON_NONE;
-                    }
-    #else
-                    uint32_t reason = RP_REASON_NONE;
-                    if (act) {
-                        const double wk = al.wheelbase * kappa;
-                        // |round(yaw, 5)| > kappa_max v           with yaw = dth / dt           (:993-995)
-                        const bool bad_yaw = fabs(rint(dth * al.c_yaw)) > al.kappa_max * v * 1e5;
-                        // |dka / dt| > v_delta_max / (wb cos^2(atan(wb kappa)))                  (:1001-1005)
-                        const bool bad_kd = fabs(kdot) > al.c_kdot * __builtin_fma(wk, wk, 1.0);
-                        // a_min <= a <= a_max (v_switch / v above the switching velocity)        (:1011-1014)
-                        const bool ok_acc = (-al.a_max <= acc) && (v > al.v_switch ? acc * v <= al.a_max * al.v_switch : acc <= al.a_max);
-                        if ((cm & RP_CHECK_VELOCITY) && v < -RP_EPS) reason = RP_REASON_VELOCITY;
-                        else if ((cm & RP_CHECK_KAPPA) && fabs(kappa) > al.kappa_max) reason = RP_REASON_KAPPA;
-                        else if ((cm & RP_CHECK_YAW_RATE) && bad_yaw) reason = RP_REASON_YAW_RATE;
-                        else if ((cm & RP_CHECK_KAPPA_DOT) && bad_kd) reason = RP_REASON_KAPPA_DOT;
-                        else if ((cm & RP_CHECK_ACCELERATION) && !ok_acc) reason = RP_REASON_ACCELERATION;
-                    }
-    #endif
+                    // -- _check_constraints, reactive_planner.py:971-1017
+                    uint32_t reason = constraint_reason(al, cm, v, acc, kappa, dth, kdot);
+                    reason = act ? reason : RP_REASON_NONE;
                     if (__any(reason != RP_REASON_NONE)) {   // wave-uniform
                         const uint64_t fm = group_ballot<G>(reason != RP_REASON_NONE, gbase);
                         const int fl = fm ? __ffsll((unsigned long long)fm) - 1 : 0;
@@ -2342,7 +2381,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                             st_row<RP_WT, RP_NT>(row_at(off8, RP_KAPPA_DOT), kdot);
                             st_row<RP_WT, RP_NT>(row_at(off8, RP_THETA_CL), th_cl);
                         }
-                        cost_acc += cost_terms(i, acc, v, s, d, th_cl);
+                        cost_acc += eval_cost_terms(i, acc, v, s, d, th_cl);
                     }
                     // static shapes: the pose's cell of the grid over them (static_grid_mask) is requested here for the valid steps,
                     // whose pose is final, and behind the extension for the extended ones -- and waited for IN FRONT of the row stores.
@@ -2394,7 +2433,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                         const double e_dd = o[12] + tk * 0.0;          // :319
                         const double e_s = o[7] + tk * o[10];          // :330
                         const double e_d = o[8] + tk * o[12];          // :331
-                        if (live) cost_acc += cost_terms(i, o[4], vt, e_s, e_d, o[9]);
+                        if (live) cost_acc += eval_cost_terms(i, o[4], vt, e_s, e_d, o[9]);
                         if (LATE_STORE) {   // what the step block's store below writes for this lane
                             v = vt; acc = o[4]; kappa = o[5]; kdot = o[6];
                             s = e_s; d = e_d; th_cl = o[9];
@@ -2593,6 +2632,61 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
 }
 
 // ------------------------------------------------------------------------------------------------
+// Shared by the two kernels with one lane per candidate (rp_cost_kernel, rp_chunk_kernel).
+// ------------------------------------------------------------------------------------------------
+// eager collision query of the rear-axle pose (x, y, cos, sin) of this lane at step i, reactive_planner.py:1033-1046: the lanes of a
+// wavefront stand at the SAME step, so the (pair, step) mask (fld(PF_NEAR)), the obstacle rows and the walk over them are (nearly)
+// uniform over the wavefront
+template <int COLL, class FLD>
+__device__ __forceinline__ bool pose_query(const KArgs &a, const FLD &fld, bool want, int i, double x, double y, double cs, double sn) {
+    const double ego_cx = x + a.wb_rear_axle * cs, ego_cy = y + a.wb_rear_axle * sn;
+    const uint64_t near_dyn = want ? double_as_mask(fld(PF_NEAR)) : 0;
+    uint64_t near_sta = 0;
+    if (COLL == 2 && want)
+        near_sta = static_grid_mask(a.obs.grid, a.obs.gx0, a.obs.gy0, a.obs.ginv, a.obs.gnx, a.obs.gny, ego_cx, ego_cy);
+    const bool ask = want && (near_dyn | near_sta) != 0;
+    if (__any(ask)) {   // wave-uniform; every lane runs the query code (wave-level culling inside)
+        const Obb ego = {ego_cx, ego_cy, cs, sn, a.half_length, a.half_width};
+        return pose_collides<true, COLL == 2, false, true>(a.obs, ego, a.ego_radius, a.time_step0 + i * a.factor, ask, near_dyn, near_sta) && ask;
+    }
+    return false;
+}
+
+// the sixteen partial sums of a candidate's cost (by step mod 16) in the order of group_sum_last<16> (lane 15's tree: ror 8, 4, 2, 1):
+// rp_eval_kernel's order of additions
+__device__ __forceinline__ double sum16_group_order(const double pj[16]) {
+    double s8[8], s4[4], s2[2];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s8[k] = pj[8 + k] + pj[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s4[k] = s8[4 + k] + s8[k];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) s2[k] = s4[2 + k] + s4[k];
+    return s2[1] + s2[0];
+}
+
+// block partial of a wavefront of 64 candidates (one per lane, `mine`): lexicographic (cost, index) min + counters
+__device__ __forceinline__ void write_wave_partial(const KArgs &a, bool mine, uint32_t status, double cost, int64_t gidx, int lane) {
+    const uint32_t lab = RP_STATUS_LABEL(status), rs = RP_STATUS_REASON(status);
+    double bc = (mine && lab == RP_LABEL_FEASIBLE && cost == cost) ? cost : 0.0;
+    long long bi = (mine && lab == RP_LABEL_FEASIBLE && cost == cost) ? (long long)gidx : -1;
+    wave_min_pair(bc, bi);
+    const Partials bp = partials_at(a.partials, a.partials_cap, a.partials_first + (int)blockIdx.x);
+    const unsigned int n_feas = (unsigned int)__popcll(__ballot(mine && (lab == RP_LABEL_FEASIBLE || lab == RP_LABEL_INFEASIBLE_COLLISION)));
+    unsigned int cnt_mine = 0;
+#pragma unroll
+    for (uint32_t r = 1; r < 8; ++r) {
+        const unsigned int cnt = (unsigned int)__popcll(__ballot(mine && rs == r));
+        cnt_mine = lane == (int)(2 + r) ? cnt : cnt_mine;
+    }
+    cnt_mine = lane == 0 ? n_feas : cnt_mine;   // [0] n_feasible, [1] n_collision, [2 + r] reasons
+    const unsigned int n_coll = (unsigned int)__popcll(__ballot(mine && lab == RP_LABEL_INFEASIBLE_COLLISION));
+    cnt_mine = lane == 1 ? n_coll : cnt_mine;
+    if (lane < RP_PARTIAL_CNT) bp.cnt[lane] = cnt_mine;
+    if (lane == 0) { bp.cost[0] = bi >= 0 ? bc : 0.0; bp.idx[0] = bi; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // rp_cost_kernel -- costs-only evaluation of LARGE grid batches, ONE LANE PER CANDIDATE, the lane walks its candidate's steps.
 //
 // What rp_eval_kernel's layout (a group of 16 lanes per candidate, lane = time step) pays for the time axis lying across lanes --
@@ -2603,9 +2697,9 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
 // step the loop is at, the extension reads registers, and what is uniform over a (T, longitudinal sample) pair -- the whole
 // profile step -- is the same for (nearly) all lanes of the wavefront.  ~165 vector instructions per (wavefront, step) for 64
 // candidates against ~290 per step block of 16 steps for 4.
-// Arithmetic: expression for expression that of rp_eval_kernel (same labels, reasons, first failing steps, costs).  The cost is
-// summed in rp_eval_kernel's order too -- sixteen partial sums by step mod 16 (one lane of the group each, there), combined in
-// the order of group_sum_last<16> -- so the two kernels agree bit for bit.
+// The per-step arithmetic is rp_eval_kernel's (the helpers above).  The cost is summed in rp_eval_kernel's order too -- sixteen
+// partial sums by step mod 16 (one lane of the group each, there), combined in the order of group_sum_last<16> -- so the two kernels
+// agree bit for bit.
 // Grid plans without the collision query (no obstacles, RP_FLAG_SKIP_COLLISION, or the first pass of the cost-ordered stage),
 // no state rows, two-kernel path (profiles from rp_lon_kernel).  One wavefront per workgroup; slot = blockIdx.x * 64 + lane.
 // ------------------------------------------------------------------------------------------------
@@ -2626,13 +2720,10 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
     const int lane = threadIdx.x;
     const int64_t count = a.count;
     const int64_t w0 = (int64_t)blockIdx.x * RP_COST_BLOCK;
-    if (a.lazy_ctl && blockIdx.x == 0 && lane < (int)(sizeof(LazyCtl) / 8))   // (first pass of the lazy stage)
-        reinterpret_cast<unsigned long long *>(a.lazy_ctl)[lane] = 0ull;
-    if (a.sweep_init && blockIdx.x == 0 && lane == 0) __hip_atomic_store(a.sweep_init, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (pass 1 of the bounded sweep)
+    clear_pass1_controls(a, lane);
     const int64_t slot = w0 + lane;
     const bool valid = slot < count;
     const int64_t gidx = a.cand_begin + (valid ? slot : w0);   // (lanes behind the batch shadow the wavefront's first candidate)
-    // ---- candidate: lateral sample, pair header, lateral polynomial (sampling.py:226-238, 268-270)
     const uint32_t g32 = (uint32_t)gidx, nd = (uint32_t)a.nD;
     const uint32_t p32 = g32 / nd;
     const double d_target = grid_base(a)[a.nT + a.nL + (int)(g32 - p32 * nd)];
@@ -2644,33 +2735,16 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
     const Poly lat = quintic_coeffs(a.x0_lat[0], a.x0_lat[1], a.x0_lat[2], d_target, 0.0, 0.0, h.lat_T);
     double P[16];
     park_poly(P, lat);
-    const int N = a.N, n = N + 1;
-    const double dt = a.dt;
-    constexpr bool low = LOW;
-    const uint32_t cm = a.constraint_mask;
-    const int mid = n / 2;
     // Horner steps as three-address v_fma_f64 (rp_math.h: rp_fma3): the coefficients stay where they are -- the compiler's two-address
     // v_fmac_f64 wants a copy of the coefficient per step (13 v_mov_b64 per time step).  Same operations as poly_pos / poly_vel / poly_acc.
     auto p_pos = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[5], t, P[4]), t, P[3]), t, P[2]), t, P[1]), t, P[0]); };
     auto p_vel = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[10], t, P[9]), t, P[8]), t, P[7]), t, P[6]); };
     auto p_acc = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(P[14], t, P[13]), t, P[12]), t, P[11]); };
-
-    auto cost_terms = [&](int i, double acc, double v, double s, double d, double th_cl) -> double {   // (rp_eval_kernel's, word for word)
-        double e, cst;
-        e = a.w_a * acc; cst = e * e;
-        e = 0.25 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
-        e = 0.25 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
-        if (a.has_speed) { e = 5.0 * (v - a.desired_speed); cst = __builtin_fma(e, e, cst); }
-        if (a.has_s) { e = 0.25 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
-        if (i == N) {
-            e = 20.0 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
-            e = 5.0 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
-            if (a.has_speed) { e = v - a.desired_speed; cst += 50.0 * (e * e); }
-            if (a.has_s) { e = 20.0 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
-        }
-        if (i == mid && a.has_speed) { e = v - a.desired_speed; cst += 100.0 * (e * e); }
-        return cst;
-    };
+    const int N = a.N, n = N + 1;
+    const double dt = a.dt;
+    constexpr bool low = LOW;
+    const uint32_t cm = a.constraint_mask;
+    const int mid = n / 2;
 
     int fail_step = -1, ood_step = -1;
     uint32_t fail_reason = RP_REASON_NONE;
@@ -2716,62 +2790,26 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
                 // -- d', d'' (:810-832)
                 const bool moving = inv_sd > 0.0;
                 double dp, dpp;
-                if (!low) {
-                    dp = dd * inv_sd;
-                    const double ddot = ddd - dp * sdd;
-                    dpp = ddot * inv_sd * inv_sd;
-                } else {
-                    dp = dd;
-                    dpp = ddd;
-                }
+                lateral_derivs(low, dd, ddd, inv_sd, sdd, dp, dpp);
                 // -- orientations (:842-873) incl. the standstill carry of :866
                 const bool use_atan = moving || low;
-                double th_cl = rp_atan(dp);
-                double th_gl = th_cl + th_ref;
-                const double w2 = __builtin_fma(dp, dp, 1.0);
-                double cosT = rp_rsqrt(w2);
-                double secT = w2 * cosT;
-                double tanT = dp;
+                double th_cl, th_gl, cosT, secT, tanT;
+                atan_angles(dp, th_ref, th_cl, th_gl, cosT, secT, tanT);
                 if (!low && __any(act && !use_atan)) {   // standstill lanes keep the orientation of the step before (:866)
                     if (!use_atan) {
                         th_gl = th_prev;
                         th_cl = th_gl - th_ref;
                     }
-                    double sn, cs;
-                    rp_sincos(th_cl, &sn, &cs);
-                    const double sc = rp_rcp(cs);
-                    cosT = use_atan ? cosT : cs;
-                    secT = use_atan ? secT : sc;
-                    tanT = use_atan ? tanT : sn * sc;
+                    standstill_angles(th_cl, use_atan, cosT, secT, tanT);
                 }
                 // -- curvature, velocity, acceleration (:883-896)
-                const double oneKrD = 1.0 - k_r * d;
-                const double q = cosT * rp_rcp(oneKrD);
-                const double kterm = frenet_kterm(k_r_d, d, k_r, dp);
-                double kappa = frenet_kappa(dpp, kterm, tanT, cosT, q, k_r);
-                const double f = oneKrD * secT;
-                double v = sd * f;
-                double acc = frenet_acc(sdd, f, sd, secT, oneKrD, tanT, kappa, k_r, kterm);
+                double kappa, v, acc;
+                frenet_kinematics(d, dp, dpp, sd, sdd, k_r, k_r_d, cosT, secT, tanT, kappa, v, acc);
                 const double dth = i > 0 ? th_gl - th_prev : 0.0;
                 const double kdot = i > 0 ? kappa - ka_prev : 0.0;
-                // -- _check_constraints, reactive_planner.py:971-1017 (order: velocity, kappa, yaw, kappa_dot, acc)
-                uint32_t reason = RP_REASON_NONE;
-                {
-                    const double a_max = a.a_max, v_switch = a.v_switch, kappa_max = a.kappa_max;
-                    const double wk = a.wheelbase * kappa;
-                    const bool bad_yaw = fabs(rint(dth * a.c_yaw)) > kappa_max * v * 1e5;
-                    const bool bad_kd = fabs(kdot) > a.c_kdot * __builtin_fma(wk, wk, 1.0);
-                    const bool fast = v > v_switch;
-                    const double acc_l = fast ? acc * v : acc, acc_r = fast ? a_max * v_switch : a_max;
-                    const bool bad_acc = !((-a_max <= acc) & (acc_l <= acc_r));
-                    const bool bad_v = v < -RP_EPS, bad_k = fabs(kappa) > kappa_max;
-                    reason = (((cm & RP_CHECK_ACCELERATION) != 0) & bad_acc) ? RP_REASON_ACCELERATION : reason;
-                    reason = (((cm & RP_CHECK_KAPPA_DOT) != 0) & bad_kd) ? RP_REASON_KAPPA_DOT : reason;
-                    reason = (((cm & RP_CHECK_YAW_RATE) != 0) & bad_yaw) ? RP_REASON_YAW_RATE : reason;
-                    reason = (((cm & RP_CHECK_KAPPA) != 0) & bad_k) ? RP_REASON_KAPPA : reason;
-                    reason = (((cm & RP_CHECK_VELOCITY) != 0) & bad_v) ? RP_REASON_VELOCITY : reason;
-                    reason = act ? reason : RP_REASON_NONE;
-                }
+                // -- _check_constraints, reactive_planner.py:971-1017
+                uint32_t reason = constraint_reason(a, cm, v, acc, kappa, dth, kdot);
+                reason = act ? reason : RP_REASON_NONE;
                 if (reason != RP_REASON_NONE && fail_step < 0) { fail_step = i; fail_reason = reason; alive = false; }
                 // -- out of the projection domain (:908-917): no reason counter, the kinematic verdict of a later step still counts
                 const bool in_dom = s_in_dom && fabs(d) <= a.proj_d_limit;
@@ -2784,7 +2822,7 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
                     pose_sin = heading_sin(fld(PF_COS_REF), fld(PF_SIN_REF), cosT, sinT);
                 }
                 if (act) {
-                    *cs_k += cost_terms(i, acc, v, s, d, th_cl);
+                    *cs_k += cost_terms(a, i, N, mid, acc, v, s, d, th_cl);
                     th_prev = th_gl;
                     ka_prev = kappa;
                 }
@@ -2798,11 +2836,9 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
             }
             if (!act) {   // i >= L: extended state (cost_function.py sums over the extended arrays)
                 const double tk = (double)(i - L + 1) * dt;   // np.arange(1, steps + 1) * dt
-                double vt = l_v + tk * l_acc;                 // :182
-                vt = vt * (vt >= 0.0 ? 1.0 : 0.0);            // :184
-                const double e_s = l_s + tk * l_sd;           // :330
-                const double e_d = l_d + tk * l_dd;           // :331
-                *cs_k += cost_terms(i, l_acc, vt, e_s, e_d, l_thcl);
+                double vt, e_s, e_d;
+                extended_state(l_v, l_acc, l_s, l_sd, l_d, l_dd, tk, vt, e_s, e_d);
+                *cs_k += cost_terms(a, i, N, mid, l_acc, vt, e_s, e_d, l_thcl);
                 if (COLL) {   // x[L:] = x[last] + cumsum(dt * v_tmp * cos(theta[last])), same for y (:195-196); heading held (:188)
                     cumx += dt * vt * l_cos;
                     cumy += dt * vt * l_sin;
@@ -2812,19 +2848,7 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
             // -- eager collision query for this pose, reactive_planner.py:1033-1046 (a candidate that has collided is not asked again:
             //    the label is all the reference keeps of a collision; the kinematic checks -- which can still turn it into
             //    INFEASIBLE_KINEMATIC -- go on)
-            if (COLL) {
-                const bool want = alive && fail_step < 0 && ood_step < 0 && !collide;
-                const double ego_cx = pose_x + a.wb_rear_axle * pose_cos, ego_cy = pose_y + a.wb_rear_axle * pose_sin;
-                const uint64_t near_dyn = want ? double_as_mask(fld(PF_NEAR)) : 0;
-                uint64_t near_sta = 0;
-                if (COLL == 2 && want)
-                    near_sta = static_grid_mask(a.obs.grid, a.obs.gx0, a.obs.gy0, a.obs.ginv, a.obs.gnx, a.obs.gny, ego_cx, ego_cy);
-                const bool ask = want && (near_dyn | near_sta) != 0;
-                if (__any(ask)) {   // wave-uniform; every lane runs the query code (wave-level culling inside)
-                    const Obb ego = {ego_cx, ego_cy, pose_cos, pose_sin, a.half_length, a.half_width};
-                    collide |= pose_collides<true, COLL == 2, false, true>(a.obs, ego, a.ego_radius, a.time_step0 + i * a.factor, ask, near_dyn, near_sta) && ask;
-                }
-            }
+            if (COLL) collide |= pose_query<COLL>(a, fld, alive && fail_step < 0 && ood_step < 0 && !collide, i, pose_x, pose_y, pose_cos, pose_sin);
         }
     }
     // ---- label, reason, cost
@@ -2834,43 +2858,16 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
     else if (fail_step >= 0) status = RP_LABEL_INFEASIBLE_KINEMATIC | (fail_reason << 4) | ((uint32_t)fail_step << 8);
     else if (ood_step >= 0) status = RP_LABEL_NONE | (RP_REASON_OUT_OF_DOMAIN << 4) | ((uint32_t)ood_step << 8);
     else status = collide ? RP_LABEL_INFEASIBLE_COLLISION : RP_LABEL_FEASIBLE;
-    // the sixteen partial sums in the order of group_sum_last<16> (lane 15's tree: ror 8, 4, 2, 1)
-    double cost;
-    {
-        double s8[8], s4[4], s2[2];
+    double pj[16];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) s8[k] = csum[(8 + k) * RP_COST_BLOCK] + csum[k * RP_COST_BLOCK];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s4[k] = s8[4 + k] + s8[k];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) s2[k] = s4[2 + k] + s4[k];
-        cost = s2[1] + s2[0];
-    }
+    for (int k = 0; k < 16; ++k) pj[k] = csum[k * RP_COST_BLOCK];
+    double cost = sum16_group_order(pj);
     if (decided_bad) cost = __builtin_nan("");
     if (valid) {
         a.status[slot] = status;
         a.cost[slot] = cost;
     }
-    // ---- block partial: lexicographic (cost, index) min + counters of this wavefront
-    if (a.partials) {
-        const uint32_t lab = RP_STATUS_LABEL(status), rs = RP_STATUS_REASON(status);
-        double bc = (valid && lab == RP_LABEL_FEASIBLE && cost == cost) ? cost : 0.0;
-        long long bi = (valid && lab == RP_LABEL_FEASIBLE && cost == cost) ? (long long)gidx : -1;
-        wave_min_pair(bc, bi);
-        const Partials bp = partials_at(a.partials, a.partials_cap, a.partials_first + (int)blockIdx.x);
-        const unsigned int n_feas = (unsigned int)__popcll(__ballot(valid && (lab == RP_LABEL_FEASIBLE || lab == RP_LABEL_INFEASIBLE_COLLISION)));
-        unsigned int mine = 0;
-#pragma unroll
-        for (uint32_t r = 1; r < 8; ++r) {
-            const unsigned int cnt = (unsigned int)__popcll(__ballot(valid && rs == r));
-            mine = lane == (int)(2 + r) ? cnt : mine;
-        }
-        mine = lane == 0 ? n_feas : mine;   // [0] n_feasible, [1] n_collision, [2 + r] reasons
-        const unsigned int n_coll = (unsigned int)__popcll(__ballot(valid && lab == RP_LABEL_INFEASIBLE_COLLISION));
-        mine = lane == 1 ? n_coll : mine;
-        if (lane < RP_PARTIAL_CNT) bp.cnt[lane] = mine;
-        if (lane == 0) { bp.cost[0] = bi >= 0 ? bc : 0.0; bp.idx[0] = bi; }
-    }
+    if (a.partials) write_wave_partial(a, valid, status, cost, gidx, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2901,7 +2898,7 @@ __global__ __launch_bounds__(RP_COST_BLOCK, COLL ? RP_WAVES_PER_SIMD : RP_COST_W
 //     tree of group_sum_last<16> -- here every lane leaves ITS block's sixteen terms in LDS and the workgroup's first wavefront forms
 //     the partial sums over the blocks in ascending order: the same additions in the same order, the same bits (rp_cost_kernel does
 //     the same inside a lane).
-// Arithmetic: expression for expression that of rp_eval_kernel / rp_cost_kernel (same labels, reasons, first failing steps, costs).
+// The per-step arithmetic is rp_eval_kernel's / rp_cost_kernel's (the shared helpers: same labels, reasons, first failing steps, costs).
 // Grid plans, no state rows, two-kernel path (profiles from rp_lon_kernel), 17 <= N + 1 <= 112 (two to seven step blocks).
 // ------------------------------------------------------------------------------------------------
 #define RP_CHUNK_BLOCK 64    // candidates per workgroup (one wavefront per step block of theirs: G * 64 threads)
@@ -2923,13 +2920,11 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);   // this wavefront's step block (wave-uniform)
     const int64_t count = a.count;
     const int64_t w0 = (int64_t)blockIdx.x * RP_CHUNK_BLOCK;
-    if (a.lazy_ctl && blockIdx.x == 0 && tid < (int)(sizeof(LazyCtl) / 8))   // (first pass of the lazy stage)
-        reinterpret_cast<unsigned long long *>(a.lazy_ctl)[tid] = 0ull;
-    if (a.sweep_init && blockIdx.x == 0 && tid == 0) __hip_atomic_store(a.sweep_init, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (pass 1 of the bounded sweep)
+    clear_pass1_controls(a, tid);
     const int64_t slot = w0 + lane;
     const bool valid = slot < count;
     const int64_t gidx = a.cand_begin + (valid ? slot : w0);   // (lanes behind the batch shadow the wavefront's first candidate)
-    // ---- candidate: lateral sample, pair header, lateral polynomial (sampling.py:226-238, 268-270)
+    // (rp_cost_kernel's candidate set-up, repeated: shared as a struct it left two more scalar registers spilled in rp_chunk_kernel)
     const uint32_t g32 = (uint32_t)gidx, nd = (uint32_t)a.nD;
     const uint32_t p32 = g32 / nd;
     const double d_target = grid_base(a)[a.nT + a.nL + (int)(g32 - p32 * nd)];
@@ -2942,31 +2937,14 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
     const Poly lat = quintic_coeffs(a.x0_lat[0], a.x0_lat[1], a.x0_lat[2], d_target, 0.0, 0.0, h.lat_T);
     double P[16];
     park_poly(P, lat);
+    auto p_pos = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[5], t, P[4]), t, P[3]), t, P[2]), t, P[1]), t, P[0]); };
+    auto p_vel = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[10], t, P[9]), t, P[8]), t, P[7]), t, P[6]); };
+    auto p_acc = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(P[14], t, P[13]), t, P[12]), t, P[11]); };
     const int N = a.N, n = N + 1;
     const double dt = a.dt;
     constexpr bool low = LOW;
     const uint32_t cm = a.constraint_mask;
     const int mid = n / 2;
-    auto p_pos = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[5], t, P[4]), t, P[3]), t, P[2]), t, P[1]), t, P[0]); };
-    auto p_vel = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(rp_fma3(P[10], t, P[9]), t, P[8]), t, P[7]), t, P[6]); };
-    auto p_acc = [&](double t) { return rp_fma3(rp_fma3(rp_fma3(P[14], t, P[13]), t, P[12]), t, P[11]); };
-
-    auto cost_terms = [&](int i, double acc, double v, double s, double d, double th_cl) -> double {   // (rp_eval_kernel's, word for word)
-        double e, cst;
-        e = a.w_a * acc; cst = e * e;
-        e = 0.25 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
-        e = 0.25 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
-        if (a.has_speed) { e = 5.0 * (v - a.desired_speed); cst = __builtin_fma(e, e, cst); }
-        if (a.has_s) { e = 0.25 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
-        if (i == N) {
-            e = 20.0 * (a.desired_d - d); cst = __builtin_fma(e, e, cst);
-            e = 5.0 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
-            if (a.has_speed) { e = v - a.desired_speed; cst += 50.0 * (e * e); }
-            if (a.has_s) { e = 20.0 * (a.desired_s - s); cst = __builtin_fma(e, e, cst); }
-        }
-        if (i == mid && a.has_speed) { e = v - a.desired_speed; cst += 100.0 * (e * e); }
-        return cst;
-    };
 
     int fail_step = -1, ood_step = -1;
     uint32_t fail_reason = RP_REASON_NONE;
@@ -3015,22 +2993,11 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
                 // -- d', d'' (:810-832)
                 const bool moving = inv_sd > 0.0;
                 double dp, dpp;
-                if (!low) {
-                    dp = dd * inv_sd;
-                    const double ddot = ddd - dp * sdd;
-                    dpp = ddot * inv_sd * inv_sd;
-                } else {
-                    dp = dd;
-                    dpp = ddd;
-                }
+                lateral_derivs(low, dd, ddd, inv_sd, sdd, dp, dpp);
                 // -- orientations (:842-873) incl. the standstill carry of :866
                 const bool use_atan = moving || low;
-                double th_cl = rp_atan(dp);
-                double th_gl = th_cl + th_ref;
-                const double w2 = __builtin_fma(dp, dp, 1.0);
-                double cosT = rp_rsqrt(w2);
-                double secT = w2 * cosT;
-                double tanT = dp;
+                double th_cl, th_gl, cosT, secT, tanT;
+                atan_angles(dp, th_ref, th_cl, th_gl, cosT, secT, tanT);
                 if (!low && __any(act && !use_atan)) {   // standstill lanes keep the orientation of the step before (:866)
                     if (pre && act && !use_atan) {
                         // the step before is not this lane's: the orientation it carries is that of the last MOVING step in front of
@@ -3053,41 +3020,16 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
                         th_gl = th_prev;
                         th_cl = th_gl - th_ref;
                     }
-                    double sn, cs;
-                    rp_sincos(th_cl, &sn, &cs);
-                    const double sc = rp_rcp(cs);
-                    cosT = use_atan ? cosT : cs;
-                    secT = use_atan ? secT : sc;
-                    tanT = use_atan ? tanT : sn * sc;
+                    standstill_angles(th_cl, use_atan, cosT, secT, tanT);
                 }
                 // -- curvature, velocity, acceleration (:883-896)
-                const double oneKrD = 1.0 - k_r * d;
-                const double qk = cosT * rp_rcp(oneKrD);
-                const double kterm = frenet_kterm(k_r_d, d, k_r, dp);
-                double kappa = frenet_kappa(dpp, kterm, tanT, cosT, qk, k_r);
-                const double f = oneKrD * secT;
-                double v = sd * f;
-                double acc = frenet_acc(sdd, f, sd, secT, oneKrD, tanT, kappa, k_r, kterm);
+                double kappa, v, acc;
+                frenet_kinematics(d, dp, dpp, sd, sdd, k_r, k_r_d, cosT, secT, tanT, kappa, v, acc);
                 const double dth = i > 0 ? th_gl - th_prev : 0.0;
                 const double kdot = i > 0 ? kappa - ka_prev : 0.0;
-                // -- _check_constraints, reactive_planner.py:971-1017 (order: velocity, kappa, yaw, kappa_dot, acc)
-                uint32_t reason = RP_REASON_NONE;
-                {
-                    const double a_max = a.a_max, v_switch = a.v_switch, kappa_max = a.kappa_max;
-                    const double wk = a.wheelbase * kappa;
-                    const bool bad_yaw = fabs(rint(dth * a.c_yaw)) > kappa_max * v * 1e5;
-                    const bool bad_kd = fabs(kdot) > a.c_kdot * __builtin_fma(wk, wk, 1.0);
-                    const bool fast = v > v_switch;
-                    const double acc_l = fast ? acc * v : acc, acc_r = fast ? a_max * v_switch : a_max;
-                    const bool bad_acc = !((-a_max <= acc) & (acc_l <= acc_r));
-                    const bool bad_v = v < -RP_EPS, bad_k = fabs(kappa) > kappa_max;
-                    reason = (((cm & RP_CHECK_ACCELERATION) != 0) & bad_acc) ? RP_REASON_ACCELERATION : reason;
-                    reason = (((cm & RP_CHECK_KAPPA_DOT) != 0) & bad_kd) ? RP_REASON_KAPPA_DOT : reason;
-                    reason = (((cm & RP_CHECK_YAW_RATE) != 0) & bad_yaw) ? RP_REASON_YAW_RATE : reason;
-                    reason = (((cm & RP_CHECK_KAPPA) != 0) & bad_k) ? RP_REASON_KAPPA : reason;
-                    reason = (((cm & RP_CHECK_VELOCITY) != 0) & bad_v) ? RP_REASON_VELOCITY : reason;
-                    reason = (act && !pre) ? reason : RP_REASON_NONE;   // (the step in front of the block is judged by the lane that owns it)
-                }
+                // -- _check_constraints, reactive_planner.py:971-1017
+                uint32_t reason = constraint_reason(a, cm, v, acc, kappa, dth, kdot);
+                reason = (act && !pre) ? reason : RP_REASON_NONE;   // (the step in front of the block is judged by the lane that owns it)
                 if (reason != RP_REASON_NONE && fail_step < 0) { fail_step = i; fail_reason = reason; alive = false; }
                 // -- out of the projection domain (:908-917): no reason counter, the kinematic verdict of a later step still counts
                 const bool in_dom = s_in_dom && fabs(d) <= a.proj_d_limit;
@@ -3100,7 +3042,7 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
                     pose_sin = heading_sin(fld(PF_COS_REF), fld(PF_SIN_REF), cosT, sinT);
                 }
                 if (act) {
-                    if (!pre) csum[j * RP_CHUNK_BLOCK] = cost_terms(i, acc, v, s, d, th_cl);
+                    if (!pre) csum[j * RP_CHUNK_BLOCK] = cost_terms(a, i, N, mid, acc, v, s, d, th_cl);
                     th_prev = th_gl;
                     ka_prev = kappa;
                 }
@@ -3118,8 +3060,8 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
                     for (int k = 0; __any(live && L + k < i_first); ++k) {
                         if (live && L + k < i_first) {
                             const double tk = (double)(k + 1) * dt;
-                            double vt = l_v + tk * l_acc;
-                            vt = vt * (vt >= 0.0 ? 1.0 : 0.0);
+                            double vt, e_s, e_d;
+                            extended_state(l_v, l_acc, l_s, l_sd, l_d, l_dd, tk, vt, e_s, e_d);
                             cumx += dt * vt * l_cos;
                             cumy += dt * vt * l_sin;
                         }
@@ -3129,11 +3071,9 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
             }
             if (live && !act) {   // i >= L: extended state (cost_function.py sums over the extended arrays)
                 const double tk = (double)(i - L + 1) * dt;   // np.arange(1, steps + 1) * dt
-                double vt = l_v + tk * l_acc;                 // :182
-                vt = vt * (vt >= 0.0 ? 1.0 : 0.0);            // :184
-                const double e_s = l_s + tk * l_sd;           // :330
-                const double e_d = l_d + tk * l_dd;           // :331
-                csum[j * RP_CHUNK_BLOCK] = cost_terms(i, l_acc, vt, e_s, e_d, l_thcl);
+                double vt, e_s, e_d;
+                extended_state(l_v, l_acc, l_s, l_sd, l_d, l_dd, tk, vt, e_s, e_d);
+                csum[j * RP_CHUNK_BLOCK] = cost_terms(a, i, N, mid, l_acc, vt, e_s, e_d, l_thcl);
                 if (COLL) {   // heading held (:188)
                     cumx += dt * vt * l_cos;
                     cumy += dt * vt * l_sin;
@@ -3141,19 +3081,7 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
                 }
             }
             // -- eager collision query for this pose, reactive_planner.py:1033-1046
-            if (COLL) {
-                const bool want = live && alive && fail_step < 0 && ood_step < 0 && !collide;
-                const double ego_cx = pose_x + a.wb_rear_axle * pose_cos, ego_cy = pose_y + a.wb_rear_axle * pose_sin;
-                const uint64_t near_dyn = want ? double_as_mask(fld(PF_NEAR)) : 0;
-                uint64_t near_sta = 0;
-                if (COLL == 2 && want)
-                    near_sta = static_grid_mask(a.obs.grid, a.obs.gx0, a.obs.gy0, a.obs.ginv, a.obs.gnx, a.obs.gny, ego_cx, ego_cy);
-                const bool ask = want && (near_dyn | near_sta) != 0;
-                if (__any(ask)) {   // wave-uniform; every lane runs the query code (wave-level culling inside)
-                    const Obb ego = {ego_cx, ego_cy, pose_cos, pose_sin, a.half_length, a.half_width};
-                    collide |= pose_collides<true, COLL == 2, false, true>(a.obs, ego, a.ego_radius, a.time_step0 + i * a.factor, ask, near_dyn, near_sta) && ask;
-                }
-            }
+            if (COLL) collide |= pose_query<COLL>(a, fld, live && alive && fail_step < 0 && ood_step < 0 && !collide, i, pose_x, pose_y, pose_cos, pose_sin);
         }
     }
     // ---- the candidate's verdict over its G blocks: the first block that failed / left the domain, any pose that collides.  Blocks are
@@ -3185,53 +3113,22 @@ __global__ __launch_bounds__(RP_CHUNK_BLOCK * RP_CHUNK_MAX_BLOCKS, COLL ? RP_WAV
     else if (ood_step >= 0) status = RP_LABEL_NONE | (RP_REASON_OUT_OF_DOMAIN << 4) | ((uint32_t)ood_step << 8);
     else status = collide ? RP_LABEL_INFEASIBLE_COLLISION : RP_LABEL_FEASIBLE;
     // sixteen partial sums by step mod 16, each over the step blocks (= the workgroup's wavefronts) in ascending order, then the tree of
-    // group_sum_last<16> (lane 15's: ror 8, 4, 2, 1) -- rp_eval_kernel's order of additions
-    double cost;
-    {
-        const lds_double gsum = (lds_double)(lds_chunk + lane);
-        const int nblocks = NB;
-        double pj[RP_CHUNK_STEPS];
+    // group_sum_last<16>
+    const lds_double gsum = (lds_double)(lds_chunk + lane);
+    double pj[RP_CHUNK_STEPS];
 #pragma unroll
-        for (int k = 0; k < RP_CHUNK_STEPS; ++k) pj[k] = gsum[k * RP_CHUNK_BLOCK];   // (0.0 + the first block's term: the term itself)
-        for (int b = 1; b < nblocks; ++b) {
+    for (int k = 0; k < RP_CHUNK_STEPS; ++k) pj[k] = gsum[k * RP_CHUNK_BLOCK];   // (0.0 + the first block's term: the term itself)
+    for (int b = 1; b < NB; ++b) {
 #pragma unroll
-            for (int k = 0; k < RP_CHUNK_STEPS; ++k) pj[k] += gsum[(b * RP_CHUNK_STEPS + k) * RP_CHUNK_BLOCK];
-        }
-        double s8[8], s4[4], s2[2];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s8[k] = pj[8 + k] + pj[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s4[k] = s8[4 + k] + s8[k];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) s2[k] = s4[2 + k] + s4[k];
-        cost = s2[1] + s2[0];
+        for (int k = 0; k < RP_CHUNK_STEPS; ++k) pj[k] += gsum[(b * RP_CHUNK_STEPS + k) * RP_CHUNK_BLOCK];
     }
+    double cost = sum16_group_order(pj);
     if (decided_bad) cost = __builtin_nan("");
-    const bool mine = valid;   // (the workgroup's first wavefront: one lane per candidate)
-    if (mine) {
+    if (valid) {   // (the workgroup's first wavefront: one lane per candidate)
         a.status[slot] = status;
         a.cost[slot] = cost;
     }
-    // ---- block partial: lexicographic (cost, index) min + counters of this wavefront
-    if (a.partials) {
-        const uint32_t lab = RP_STATUS_LABEL(status), rs = RP_STATUS_REASON(status);
-        double bc = (mine && lab == RP_LABEL_FEASIBLE && cost == cost) ? cost : 0.0;
-        long long bi = (mine && lab == RP_LABEL_FEASIBLE && cost == cost) ? (long long)gidx : -1;
-        wave_min_pair(bc, bi);
-        const Partials bp = partials_at(a.partials, a.partials_cap, a.partials_first + (int)blockIdx.x);
-        const unsigned int n_feas = (unsigned int)__popcll(__ballot(mine && (lab == RP_LABEL_FEASIBLE || lab == RP_LABEL_INFEASIBLE_COLLISION)));
-        unsigned int cnt_mine = 0;
-#pragma unroll
-        for (uint32_t r = 1; r < 8; ++r) {
-            const unsigned int cnt = (unsigned int)__popcll(__ballot(mine && rs == r));
-            cnt_mine = lane == (int)(2 + r) ? cnt : cnt_mine;
-        }
-        cnt_mine = lane == 0 ? n_feas : cnt_mine;   // [0] n_feasible, [1] n_collision, [2 + r] reasons
-        const unsigned int n_coll = (unsigned int)__popcll(__ballot(mine && lab == RP_LABEL_INFEASIBLE_COLLISION));
-        cnt_mine = lane == 1 ? n_coll : cnt_mine;
-        if (lane < RP_PARTIAL_CNT) bp.cnt[lane] = cnt_mine;
-        if (lane == 0) { bp.cost[0] = bi >= 0 ? bc : 0.0; bp.idx[0] = bi; }
-    }
+    if (a.partials) write_wave_partial(a, valid, status, cost, gidx, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
