@@ -8,7 +8,7 @@
  * or imports anything from oracle/ and fails loudly when the HIP library is missing.
  *
  * Parity status: PINNED for everything that is arithmetic of the reference itself -- checked
- * against the 18 golden fixtures in tests/golden (npz files) that were produced by running the
+ * against the 94 golden fixtures in tests/golden (npz files) that were produced by running the
  * reference's own Python (tests/golden/make_golden.py); see tests/test_oracle_golden.py.
  * UNPINNED at the two third-party boundaries whose source is not under /root/reference
  * (pycrccosy (s,d)->(x,y) and pycrcc overlap tests, commonroad-drivability-checker 2024.1):

@@ -1,6 +1,8 @@
 """rp_chunk_kernel (one lane per candidate and step block of 16) against rp_eval_kernel (16 lanes per candidate) and rp_cost_kernel (one lane
 per candidate) on costs-only plans: the same status words and the same cost BITS, the step time (compiled-free: ctx.plan without winner
 rows) and the evaluation kernel's own time (HIP events on the launch) of each.
+The identity itself is ASSERTED by tests/test_kernel_bit_identity.py (edge cases, random cases, these workloads); the costbits== column here is
+a print-out beside the timings.
 usage (GPU box): python profiles/probe_chunk_kernel.py [cfg3 cfg3f cfg3rb cfg4 cfg2 ...]"""
 import os, sys, time
 import numpy as np
