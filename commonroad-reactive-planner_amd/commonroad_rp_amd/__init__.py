@@ -1,0 +1,1 @@
+from .trajectory_check import TrajectoryChecker, TrajectoryCheckResult  # noqa: F401

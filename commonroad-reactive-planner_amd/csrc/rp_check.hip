@@ -1,0 +1,353 @@
+// rp_check.hip -- librp_check.so: the batch collision checker of include/rp_check.h (MI355X / gfx950).
+//
+// K given trajectories x n poses x M obstacles: no sampling grid, no costs, no reference path, and nothing shared with a
+// planning context.  The narrow phase is the planner's (rp_device.h: Obb, obb_obb, obb_tri, obb_circ, merge_swept), so a verdict
+// is the boolean the planner's kernels produce; the tables are laid out for THIS kernel's wavefronts -- 64 consecutive poses of
+// one trajectory -- not for the planner's (neighbouring candidates: clusters, slots and the static grid of rp_host.hip stay there).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "rp_device.h"
+#include "../../include/rp_check.h"
+
+namespace {
+
+constexpr int CK_BLOCK = 256;                   // four wavefronts per workgroup
+constexpr int CK_WAVES = CK_BLOCK / 64;
+constexpr int CK_ROW = 10;                      // doubles per static row (below)
+constexpr int CK_LDS_ROWS = 128;                // static rows staged in LDS (10 KiB per workgroup); more: read from device memory
+constexpr int32_t CK_NONE = 0x7f7f7f7f;         // "no hit yet" of the first-hit arrays (a byte fill), above every pose index
+
+// Static shapes as ONE table, rectangles first, then triangles, then circles; every lane of a wavefront reads the same row
+// (a broadcast from LDS, or a scalar load).  Row: [0..5] the shape -- rectangle cx, cy, ux, uy, hl, hw | triangle x1 .. y3 |
+// circle cx, cy, r -- then [6..8] its bounding circle cx, cy, r and one double of padding.
+// Dynamic rectangles: struct-of-arrays planes [7][n_dyn][n_steps] cx, cy, ux, uy, hl, hw, r_bound (cx = NaN: absent), so that the
+// lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
+struct CkTables {
+    const double *stat;
+    const double *dyn;
+    int32_t n_sobb, n_tri, n_circ, n_dyn, n_steps, dyn_t0;
+};
+
+typedef const double __attribute__((address_space(3))) *lds_cdouble;
+
+// cc.collide(rectangle e at scenario time index t) for the lanes that `want` it.  Every lane of the wavefront calls this.
+// r: radius of a circle around e (bounding-circle rejection in front of every exact test; the small relative margin keeps it from
+// rejecting a pair the exact test would accept).  A lane stops at its first hit.
+template <bool LDS>
+__device__ __forceinline__ bool ck_collides(const CkTables &tb, const double *lds_rows, const Obb &e, double r, long long t, bool want) {
+    bool hit = false;
+    auto row = [&](int j, int q) -> double {
+        if constexpr (LDS) return ((lds_cdouble)lds_rows)[j * CK_ROW + q];
+        else return ((gcdouble)tb.stat)[(size_t)j * CK_ROW + q];
+    };
+    const int n_static = tb.n_sobb + tb.n_tri + tb.n_circ;
+    for (int j = 0; j < n_static; ++j) {   // wave-uniform
+        const double dx = row(j, 6) - e.cx, dy = row(j, 7) - e.cy, rr = r + row(j, 8);
+        if (want && !hit && dx * dx + dy * dy <= rr * rr * 1.000001) {   // false for NaN
+            if (j < tb.n_sobb) {
+                const Obb b = {row(j, 0), row(j, 1), row(j, 2), row(j, 3), row(j, 4), row(j, 5)};
+                hit = obb_obb(e, b);
+            } else if (j < tb.n_sobb + tb.n_tri) {
+                const double tv[6] = {row(j, 0), row(j, 1), row(j, 2), row(j, 3), row(j, 4), row(j, 5)};
+                hit = obb_tri(e, tv);
+            } else {
+                hit = obb_circ(e, row(j, 0), row(j, 1), row(j, 2));
+            }
+        }
+    }
+    // dynamic rectangles at the lane's own time index; outside the table: absent
+    const long long k = t - (long long)tb.dyn_t0;
+    const bool in_table = want && k >= 0 && k < (long long)tb.n_steps;
+    const size_t kc = in_table ? (size_t)k : 0;
+    const size_t plane = (size_t)tb.n_dyn * (size_t)tb.n_steps;
+    const gcdouble dyn = (gcdouble)tb.dyn;
+    for (int j = 0; j < tb.n_dyn; ++j) {
+        const bool open = in_table && !hit;
+        if (!__any(open)) break;   // the wavefront goes on while any lane is unresolved
+        const gcdouble o = dyn + (size_t)j * (size_t)tb.n_steps + kc;
+        const double cx = o[0], cy = o[plane], rr = r + o[6 * plane];
+        const double dx = cx - e.cx, dy = cy - e.cy;
+        if (open && dx * dx + dy * dy <= rr * rr * 1.000001) {   // false for NaN: absent
+            const Obb b = {cx, cy, o[2 * plane], o[3 * plane], o[4 * plane], o[5 * plane]};
+            hit = obb_obb(e, b);
+        }
+    }
+    return hit;
+}
+
+// A lane is a pose (and the segment that starts at it), a wavefront 64 consecutive poses of one trajectory: wavefront w of the
+// grid = chunk w % nchunk of trajectory w / nchunk.  poses: planes x | y | theta, each [K][n].  first_pose / first_seg hold CK_NONE
+// on entry (a fill in front of the launch) and receive the smallest colliding index by one atomicMin per wavefront that has a hit.
+template <bool LDS>
+__global__ __launch_bounds__(CK_BLOCK) void rp_check_batch_kernel(CkTables tb, const double *poses, const int32_t *len, int K, int n, int nchunk,
+                                                                  uint32_t mode, double wb_rear_axle, double hl, double hw, int t0, int factor,
+                                                                  int32_t *first_pose, int32_t *first_seg, uint8_t *pose_hit,
+                                                                  unsigned long long *red) {
+    __shared__ double sh_rows[LDS ? CK_LDS_ROWS * CK_ROW : 1];
+    if (LDS) {
+        const int nd = (tb.n_sobb + tb.n_tri + tb.n_circ) * CK_ROW;   // <= CK_LDS_ROWS * CK_ROW: the host picks this variant
+        for (int q = threadIdx.x; q < nd; q += CK_BLOCK) sh_rows[q] = tb.stat[q];
+        __syncthreads();
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { red[0] = ~0ull; red[1] = 0ull; }   // for rp_check_reduce_kernel, behind this launch
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * CK_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (w >= (long long)K * nchunk) return;   // (a whole wavefront, behind the only barrier)
+    const int k = (int)(w / nchunk), chunk = (int)(w % nchunk);
+    const int i = chunk * 64 + lane;
+    const int L = len ? len[k] : n;           // 1 <= L <= n, checked by the host
+    const bool have = i < L;
+    const size_t plane = (size_t)K * (size_t)n;
+    const size_t at = (size_t)k * (size_t)n + (size_t)(have ? i : 0);   // lanes behind the end: pose 0, never asked
+    double s, c;
+    sincos(poses[2 * plane + at], &s, &c);
+    const Obb ego = {poses[at] + wb_rear_axle * c, poses[plane + at] + wb_rear_axle * s, c, s, hl, hw};
+
+    if (mode & RP_TRAJ_POSES) {
+        const bool hit = ck_collides<LDS>(tb, sh_rows, ego, sqrt(hl * hl + hw * hw), (long long)t0 + (long long)i * factor, have);
+        if (pose_hit && i < n) pose_hit[(size_t)k * (size_t)n + (size_t)i] = hit ? 1 : 0;
+        const unsigned long long b = __ballot(hit);
+        if (b != 0 && lane == 0) atomicMin(&first_pose[k], chunk * 64 + (__ffsll(b) - 1));
+    }
+    if (mode & RP_TRAJ_SWEPT) {
+        // the rectangle of pose i + 1 comes from the next lane; the wavefront's last lane loads that pose itself
+        const bool seg = i + 1 < L;
+        Obb nxt = {__shfl_down(ego.cx, 1), __shfl_down(ego.cy, 1), __shfl_down(ego.ux, 1), __shfl_down(ego.uy, 1), hl, hw};
+        if (lane == 63 && seg) {
+            double s1, c1;
+            sincos(poses[2 * plane + at + 1], &s1, &c1);
+            nxt.cx = poses[at + 1] + wb_rear_axle * c1; nxt.cy = poses[plane + at + 1] + wb_rear_axle * s1; nxt.ux = c1; nxt.uy = s1;
+        }
+        const Obb m = merge_swept(ego, seg ? nxt : ego);
+        const bool hit = ck_collides<LDS>(tb, sh_rows, m, sqrt(m.hl * m.hl + m.hw * m.hw), (long long)t0 + (long long)i, seg);
+        const unsigned long long b = __ballot(hit);
+        if (b != 0 && lane == 0) atomicMin(&first_seg[k], chunk * 64 + (__ffsll(b) - 1));
+    }
+}
+
+// One lane per trajectory: CK_NONE -> -1 in the first-hit arrays, then red[0] = smallest k without a requested hit (~0: none),
+// red[1] = trajectories with one -- a ballot per wavefront, one atomic each per wavefront.
+__global__ __launch_bounds__(CK_BLOCK) void rp_check_reduce_kernel(int K, int32_t *first_pose, int32_t *first_seg, unsigned long long *red) {
+    const int k = blockIdx.x * CK_BLOCK + threadIdx.x;
+    const bool in = k < K;
+    int32_t fp = in ? first_pose[k] : -1, fs = in ? first_seg[k] : -1;
+    fp = fp >= CK_NONE ? -1 : fp;
+    fs = fs >= CK_NONE ? -1 : fs;
+    if (in) { first_pose[k] = fp; first_seg[k] = fs; }
+    const bool hit = fp >= 0 || fs >= 0;
+    const unsigned long long bh = __ballot(in && hit), bf = __ballot(in && !hit);
+    if ((threadIdx.x & 63) == 0) {
+        if (bh != 0) atomicAdd(&red[1], (unsigned long long)__popcll(bh));
+        if (bf != 0) atomicMin(&red[0], (unsigned long long)(k + (__ffsll(bf) - 1)));
+    }
+}
+
+}  // namespace
+
+struct rp_checker {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    CkTables tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};
+    double *d_stat = nullptr, *d_dyn = nullptr;
+    // poses (and lengths) of a call: pinned host block and its device copy; results likewise.  They grow on demand.
+    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
+    size_t cap_in = 0, cap_out = 0;
+};
+
+namespace {
+
+int fail(rp_checker *ck, int code, const std::string &msg) {
+    ck->err = msg;
+    return code;
+}
+
+#define CK_TRY(ck, expr)                                                                      \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(ck, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
+    } while (0)
+
+int upload(rp_checker *ck, double *&dst, const std::vector<double> &src) {
+    if (dst) { CK_TRY(ck, hipFree(dst)); dst = nullptr; }
+    if (src.empty()) return RP_OK;
+    CK_TRY(ck, hipMalloc((void **)&dst, src.size() * sizeof(double)));
+    CK_TRY(ck, hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
+    return RP_OK;
+}
+
+int grow_pair(rp_checker *ck, void *&host, void *&dev, size_t &cap, size_t need) {
+    if (need <= cap) return RP_OK;
+    if (host) { CK_TRY(ck, hipHostFree(host)); host = nullptr; }
+    if (dev) { CK_TRY(ck, hipFree(dev)); dev = nullptr; }
+    cap = 0;
+    const size_t want = need < 65536 ? 65536 : need + need / 4;
+    if (hipHostMalloc(&host, want, hipHostMallocDefault) != hipSuccess) { host = nullptr; return fail(ck, RP_ENOMEM, "rp_checker_check: pinned host memory"); }
+    if (hipMalloc(&dev, want) != hipSuccess) { dev = nullptr; return fail(ck, RP_ENOMEM, "rp_checker_check: device memory"); }
+    cap = want;
+    return RP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rp_checker_abi_version(void) { return RP_CHECKER_ABI_VERSION; }
+
+int rp_checker_create(rp_checker **out, int device) {
+    if (!out) return RP_EINVAL;
+    *out = nullptr;
+    rp_checker *ck = new (std::nothrow) rp_checker();
+    if (!ck) return RP_ENOMEM;
+    *out = ck;   // returned even on failure so that rp_checker_last_error works; the caller destroys it
+    ck->device = device;
+    int ndev = 0;
+    CK_TRY(ck, hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(ck, RP_EINVAL, "no such HIP device");
+    CK_TRY(ck, hipSetDevice(device));
+    CK_TRY(ck, hipStreamCreateWithFlags(&ck->stream, hipStreamNonBlocking));
+    return RP_OK;
+}
+
+void rp_checker_destroy(rp_checker *ck) {
+    if (!ck) return;
+    (void)hipSetDevice(ck->device);
+    if (ck->stream) (void)hipStreamSynchronize(ck->stream);
+    void *dev[] = {ck->d_stat, ck->d_dyn, ck->d_in, ck->d_out};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    if (ck->h_in) (void)hipHostFree(ck->h_in);
+    if (ck->h_out) (void)hipHostFree(ck->h_out);
+    if (ck->stream) (void)hipStreamDestroy(ck->stream);
+    delete ck;
+}
+
+const char *rp_checker_last_error(const rp_checker *ck) { return ck ? ck->err.c_str() : "null checker"; }
+
+int rp_checker_set_obstacles(rp_checker *ck, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ,
+                             const double *circ, int32_t n_dyn, int32_t n_steps, int32_t dyn_t0, const double *dyn) {
+    if (!ck) return RP_EINVAL;
+    if (!ck->stream) return fail(ck, RP_ESTATE, "rp_checker_set_obstacles: the checker has no device (rp_checker_create failed)");
+    if (n_sobb < 0 || n_tri < 0 || n_circ < 0 || n_dyn < 0 || n_steps < 0 || (n_sobb && !sobb) || (n_tri && !tri) || (n_circ && !circ) ||
+        (n_dyn && n_steps && !dyn))
+        return fail(ck, RP_EINVAL, "rp_checker_set_obstacles: negative count or null table");
+    if ((int64_t)n_sobb + n_tri + n_circ > INT32_MAX / CK_ROW) return fail(ck, RP_EINVAL, "rp_checker_set_obstacles: too many static shapes");
+    CK_TRY(ck, hipSetDevice(ck->device));
+    CK_TRY(ck, hipStreamSynchronize(ck->stream));
+    std::vector<double> a, e;
+    try {
+        a.assign(((size_t)n_sobb + (size_t)n_tri + (size_t)n_circ) * CK_ROW, 0.0);
+        e.assign((size_t)7 * (size_t)n_dyn * (size_t)n_steps, 0.0);
+    } catch (const std::bad_alloc &) {
+        return fail(ck, RP_ENOMEM, "rp_checker_set_obstacles: host memory");
+    }
+    double *r = a.data();
+    for (int j = 0; j < n_sobb; ++j, r += CK_ROW) {   // (ux, uy from the host's cos / sin, as rp_set_obstacles)
+        const double *o = sobb + 5 * (size_t)j;
+        r[0] = o[0]; r[1] = o[1]; r[2] = std::cos(o[2]); r[3] = std::sin(o[2]); r[4] = o[3]; r[5] = o[4];
+        r[6] = o[0]; r[7] = o[1]; r[8] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
+    }
+    for (int j = 0; j < n_tri; ++j, r += CK_ROW) {
+        const double *o = tri + 6 * (size_t)j;
+        for (int q = 0; q < 6; ++q) r[q] = o[q];
+        const double bx = (o[0] + o[2] + o[4]) / 3.0, by = (o[1] + o[3] + o[5]) / 3.0;
+        double rr = 0.0;
+        for (int q = 0; q < 3; ++q) rr = std::fmax(rr, std::hypot(o[2 * q] - bx, o[2 * q + 1] - by));
+        r[6] = bx; r[7] = by; r[8] = rr;
+    }
+    for (int j = 0; j < n_circ; ++j, r += CK_ROW) {
+        const double *o = circ + 3 * (size_t)j;
+        r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
+        r[6] = o[0]; r[7] = o[1]; r[8] = o[2];
+    }
+    const size_t plane = (size_t)n_dyn * (size_t)n_steps;
+    for (size_t at = 0; at < plane; ++at) {
+        const double *o = dyn + 5 * at;
+        e[at] = o[0]; e[plane + at] = o[1];
+        e[2 * plane + at] = std::cos(o[2]); e[3 * plane + at] = std::sin(o[2]);
+        e[4 * plane + at] = o[3]; e[5 * plane + at] = o[4];
+        e[6 * plane + at] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
+    }
+    ck->tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};   // (a failed upload leaves empty tables, never half of the new ones)
+    int rc;
+    if ((rc = upload(ck, ck->d_stat, a)) != RP_OK) return rc;
+    if ((rc = upload(ck, ck->d_dyn, e)) != RP_OK) return rc;
+    ck->tb = {ck->d_stat, ck->d_dyn, n_sobb, n_tri, n_circ, plane ? n_dyn : 0, plane ? n_steps : 0, dyn_t0};
+    return RP_OK;
+}
+
+int rp_checker_check(rp_checker *ck, const rp_params *p, uint32_t mode, int64_t K, int32_t n_poses, const double *x, const double *y,
+                     const double *theta, const int32_t *len, int32_t *first_pose_hit, int32_t *first_segment_hit, uint8_t *pose_hit,
+                     int64_t *first_free, int64_t *n_hit) {
+    if (!ck) return RP_EINVAL;
+    if (!p) return fail(ck, RP_EINVAL, "rp_checker_check: null params");
+    if (p->struct_size != sizeof(rp_params)) return fail(ck, RP_EABI, "rp_checker_check: rp_params.struct_size is not this library's sizeof(rp_params)");
+    if (mode == 0 || (mode & ~(RP_TRAJ_POSES | RP_TRAJ_SWEPT)) != 0) return fail(ck, RP_EINVAL, "rp_checker_check: mode must be RP_TRAJ_POSES, RP_TRAJ_SWEPT or both");
+    if (K < 0 || n_poses < 1) return fail(ck, RP_EINVAL, "rp_checker_check: K < 0 or n_poses < 1");
+    if (K > RP_CHECKER_MAX_POSES || K * (int64_t)n_poses > RP_CHECKER_MAX_POSES)
+        return fail(ck, RP_EINVAL, "rp_checker_check: K * n_poses beyond RP_CHECKER_MAX_POSES");
+    if (!(mode & RP_TRAJ_POSES) && (first_pose_hit || pose_hit)) return fail(ck, RP_EINVAL, "rp_checker_check: first_pose_hit / pose_hit without RP_TRAJ_POSES");
+    if (!(mode & RP_TRAJ_SWEPT) && first_segment_hit) return fail(ck, RP_EINVAL, "rp_checker_check: first_segment_hit without RP_TRAJ_SWEPT");
+    if (K > 0 && (!x || !y || !theta)) return fail(ck, RP_EINVAL, "rp_checker_check: null poses");
+    if (len)
+        for (int64_t k = 0; k < K; ++k)
+            if (len[k] < 1 || len[k] > n_poses) return fail(ck, RP_EINVAL, "rp_checker_check: len[" + std::to_string(k) + "] outside 1 .. n_poses");
+    if (K == 0) {
+        if (first_free) *first_free = -1;
+        if (n_hit) *n_hit = 0;
+        return RP_OK;
+    }
+    if (!ck->stream) return fail(ck, RP_ESTATE, "rp_checker_check: the checker has no device (rp_checker_create failed)");
+    CK_TRY(ck, hipSetDevice(ck->device));
+    const size_t P = (size_t)K * (size_t)n_poses;
+    const size_t in_bytes = 3 * P * sizeof(double) + (len ? (size_t)K * sizeof(int32_t) : 0);
+    const size_t first_off = 2 * sizeof(unsigned long long), hits_off = first_off + 2 * (size_t)K * sizeof(int32_t);
+    const size_t out_bytes = hits_off + (pose_hit ? P : 0);
+    int rc;
+    if ((rc = grow_pair(ck, ck->h_in, ck->d_in, ck->cap_in, in_bytes)) != RP_OK) return rc;
+    if ((rc = grow_pair(ck, ck->h_out, ck->d_out, ck->cap_out, out_bytes)) != RP_OK) return rc;
+    double *h_poses = static_cast<double *>(ck->h_in);
+    std::memcpy(h_poses, x, P * sizeof(double));
+    std::memcpy(h_poses + P, y, P * sizeof(double));
+    std::memcpy(h_poses + 2 * P, theta, P * sizeof(double));
+    if (len) std::memcpy(h_poses + 3 * P, len, (size_t)K * sizeof(int32_t));
+    CK_TRY(ck, hipMemcpyAsync(ck->d_in, ck->h_in, in_bytes, hipMemcpyHostToDevice, ck->stream));
+    char *d_out = static_cast<char *>(ck->d_out);
+    unsigned long long *d_red = reinterpret_cast<unsigned long long *>(d_out);
+    int32_t *d_first_pose = reinterpret_cast<int32_t *>(d_out + first_off), *d_first_seg = d_first_pose + K;
+    uint8_t *d_hits = pose_hit ? reinterpret_cast<uint8_t *>(d_out + hits_off) : nullptr;
+    CK_TRY(ck, hipMemsetAsync(d_first_pose, 0x7f, 2 * (size_t)K * sizeof(int32_t), ck->stream));
+    const double *d_poses = static_cast<const double *>(ck->d_in);
+    const int32_t *d_len = len ? reinterpret_cast<const int32_t *>(d_poses + 3 * P) : nullptr;
+    const int nchunk = (n_poses + 63) / 64;
+    const long long waves = (long long)K * nchunk;
+    const unsigned grid = (unsigned)((waves + CK_WAVES - 1) / CK_WAVES);
+    const bool in_lds = ck->tb.n_sobb + ck->tb.n_tri + ck->tb.n_circ <= CK_LDS_ROWS;
+    const auto kernel = in_lds ? rp_check_batch_kernel<true> : rp_check_batch_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CK_BLOCK), 0, ck->stream, ck->tb, d_poses, d_len, (int)K, (int)n_poses, nchunk, mode,
+                       p->wb_rear_axle, 0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor, d_first_pose, d_first_seg, d_hits,
+                       d_red);
+    CK_TRY(ck, hipGetLastError());
+    hipLaunchKernelGGL(rp_check_reduce_kernel, dim3((unsigned)((K + CK_BLOCK - 1) / CK_BLOCK)), dim3(CK_BLOCK), 0, ck->stream, (int)K, d_first_pose,
+                       d_first_seg, d_red);
+    CK_TRY(ck, hipGetLastError());
+    CK_TRY(ck, hipMemcpyAsync(ck->h_out, ck->d_out, out_bytes, hipMemcpyDeviceToHost, ck->stream));
+    CK_TRY(ck, hipStreamSynchronize(ck->stream));
+    const char *h_out = static_cast<const char *>(ck->h_out);
+    const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
+    if (first_free) *first_free = h_red[0] < (unsigned long long)K ? (int64_t)h_red[0] : -1;
+    if (n_hit) *n_hit = (int64_t)h_red[1];
+    if (first_pose_hit) std::memcpy(first_pose_hit, h_out + first_off, (size_t)K * sizeof(int32_t));
+    if (first_segment_hit) std::memcpy(first_segment_hit, h_out + first_off + (size_t)K * sizeof(int32_t), (size_t)K * sizeof(int32_t));
+    if (pose_hit) std::memcpy(pose_hit, h_out + hits_off, P);
+    return RP_OK;
+}
+
+}  // extern "C"
