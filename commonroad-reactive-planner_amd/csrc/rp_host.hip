@@ -64,6 +64,7 @@ struct Options {
     int fused_lon_blocks = -1;   // ... up to this many workgroups (-1: 4 per CU)
     int auto_materialize = 1;    // small batches whose winner rows are wanted write every candidate's rows
     int stage_out = 1, row_padding = 1, row_align = 0, tail_split = 1;   // layout of the state rows in device memory
+    int fixed_stride = 1;        // fixed-stride variant of the 16-lane kernel that stores state rows (rows of 64 doubles, no split tail): 1 = by layout, 0 never
     int table_window = 1;        // single-launch variant stages only the part of the reference tables a plan can touch
     int fold_threshold = kFoldThreshold;
     int lon_publish = 1, inline_grids = 1, event_bracket = 0, winner_lanes_as_batch = 0, zero_copy = 1, coeff_groups = 1;
@@ -92,6 +93,7 @@ const OptionDesc kOptionTable[] = {
     {"row_padding", &Options::row_padding, "RP_AMD_NO_ROW_PADDING", true, 0, 1},
     {"row_align", &Options::row_align, "RP_AMD_ROW_ALIGN", false, 0, 16},
     {"tail_split", &Options::tail_split, "RP_AMD_NO_TAIL_SPLIT", true, 0, 1},
+    {"fixed_stride", &Options::fixed_stride, "RP_AMD_NO_FIXED_STRIDE", true, 0, 1},
     {"table_window", &Options::table_window, "RP_AMD_NO_TABLE_WINDOW", true, 0, 1},
     {"fold_threshold", &Options::fold_threshold, "RP_AMD_FOLD_THRESHOLD", false, 1, 1 << 30},
     {"lon_publish", &Options::lon_publish, "RP_AMD_NO_LON_PUBLISH", true, 0, 1},
@@ -183,6 +185,7 @@ struct rp_ctx {
     int lazy_skip = 0, lazy_penalty = 0;   // plans that go eager straight away after a lazy attempt had to fall back (doubles per failure, up to 64)
     int collision_mode = RP_COLLISION_AUTO;   // rp_set_collision_path
     int last_kernel = 0;                   // rp_last_kernel: which kernel evaluated the last plan's batch (RP_KERNEL_*)
+    int last_fixed_stride = 0;             // ... and whether that was rp_eval_kernel's fixed-stride variant (read-only option "last_fixed_stride")
     int last_lazy = 0;                     // 0: the last plan ran eager, 1: lazy, 2: lazy attempt + eager fallback (diagnostic, rp_last_path)
     double last_best_cost = 0.0;           // winner of the last collected plan (rp_count_collisions_before after a cost-ordered plan)
     int64_t last_best_index = -1;
@@ -383,8 +386,21 @@ const void *chunk_kernel_fn(bool low, int coll) {
     return coll == 2 ? (const void *)rp_chunk_kernel<false, 2> : (coll == 1 ? (const void *)rp_chunk_kernel<false, 1> : (const void *)rp_chunk_kernel<false, 0>);
 }
 
+// The fixed-stride variant of the 16-lane kernel that stores state rows (rp_kernels.h: ROW64) is taken by the LAYOUT of the rows:
+// 64 doubles apart, no split tail -- padded rows of 17 .. 64 steps (state_layout).  Option "fixed_stride" = 0 pins the generic variant.
+inline bool fixed_stride_applies(const rp_ctx *c, const KArgs &ka) {
+    return ka.row_stride == RP_ROW64 && ka.tail_split == 0 && ka.N + 1 > 16 && ka.N + 1 <= RP_ROW64 && c->opt.fixed_stride != 0;
+}
+
 template <int G, bool MAT, bool CIN, int COLL, bool STAGE>
 void launch_eval_tcs(rp_ctx *c, const KArgs &ka, int grid, size_t lds, int block = RP_BLOCK) {
+    if constexpr (G == 16 && MAT && !STAGE) {   // rows of 64 doubles, no split tail (17 <= N + 1 <= 64, padded rows): the fixed-stride variant
+        if (fixed_stride_applies(c, ka)) {
+            if (block == 64) launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, 64, false, true>, grid, 64, lds, ka);
+            else launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, RP_BLOCK, false, true>, grid, RP_BLOCK, lds, ka);
+            return;
+        }
+    }
     if constexpr (G == 16 && !STAGE) {   // one wavefront per workgroup (large batches of the two-kernel path: eval_block)
         if (block == 64) {
             if (ka.N + 1 <= G) launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, true, false, false, 64>, grid, 64, lds, ka);
@@ -1015,6 +1031,7 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             if (which == 1) {
                 main_grid = (int)((count + RP_COST_BLOCK - 1) / RP_COST_BLOCK);
                 c->last_kernel = RP_KERNEL_COST;
+                c->last_fixed_stride = 0;
                 const void *fn = k.low_vel_mode
                     ? (coll == 2 ? (const void *)rp_cost_kernel<true, 2> : coll == 1 ? (const void *)rp_cost_kernel<true, 1> : (const void *)rp_cost_kernel<true, 0>)
                     : (coll == 2 ? (const void *)rp_cost_kernel<false, 2> : coll == 1 ? (const void *)rp_cost_kernel<false, 1> : (const void *)rp_cost_kernel<false, 0>);
@@ -1022,10 +1039,12 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             } else if (which == 2) {
                 main_grid = (int)((count + RP_CHUNK_BLOCK - 1) / RP_CHUNK_BLOCK);   // 64 candidates per workgroup, one wavefront per step block
                 c->last_kernel = RP_KERNEL_CHUNK;
+                c->last_fixed_stride = 0;
                 launch_kargs(c, chunk_kernel_fn(k.low_vel_mode != 0, coll), main_grid, RP_CHUNK_BLOCK * chunk_G, rp_chunk_lds_bytes(chunk_G), k);
             } else {
                 main_grid = grid;
                 c->last_kernel = RP_KERNEL_EVAL;
+                c->last_fixed_stride = !fused_lds && mat_ && G == 16 && fixed_stride_applies(c, k);   // (as launch_eval_tcs decides)
                 if (fused_lds) launch_eval_fused(c, k, grid, mat_, cin, fused_lds, G);
                 else launch_eval(c, k, grid, mat_, cin, G, block);
             }
@@ -1448,6 +1467,7 @@ int rp_set_option(rp_ctx *c, const char *key, int64_t value) {
 int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (!c || !value) return RP_EINVAL;
     if (key && std::strcmp(key, "wait_fallbacks") == 0) { *value = c->wait_fallbacks; return RP_OK; }   // (read-only counter)
+    if (key && std::strcmp(key, "last_fixed_stride") == 0) { *value = c->last_fixed_stride; return RP_OK; }   // (read-only: the last plan's batch)
     const OptionDesc *d = find_option(key);
     if (!d) return RP_EINVAL;
     *value = c->opt.*(d->field);

@@ -1102,6 +1102,8 @@ __device__ __forceinline__ double frenet_acc(double sdd, double f, double sd, do
 
 // this lane's share of the cost of one (possibly extended) state, cost_function.py:51-71 / 82-92: every step adds its own terms, steps
 // N and N/2 (mid = int(len(v) / 2), cost_function.py:59) also the terminal ones
+// (the parameters cost_terms reads, for a caller that has fetched them: rp_eval_kernel's fixed-stride variant)
+struct CostParams { double w_a, desired_speed, desired_d, desired_s; int32_t has_speed, has_s; };
 template <class KA>
 __device__ __forceinline__ double cost_terms(const KA &a, int i, int N, int mid, double acc, double v, double s, double d, double th_cl) {
     double e, cst;
@@ -1799,9 +1801,16 @@ __device__ __forceinline__ CandIn fetch_candidate(const KArgs &a, int64_t gidx, 
 // workgroup finish far apart (in-kernel stamps on cfg3: the first at 30 k cycles, the workgroup at 42 k).
 // SWEEP: the bounded collision sweep (KArgs::sweep_bound) -- a variant of its own (16 lanes per candidate, no state rows, two-kernel path):
 // as a run-time switch of the plain variants it cost them two more spilled registers and 3.5 % (cfg3 eager 93.6 -> 97.0 us).
-template <int G, bool MAT, bool COEFFS_IN, int COLL, bool ONE_CHUNK, bool STAGE_OUT, bool LON_FUSED, int BLOCK = RP_BLOCK, bool SWEEP = false>
+// ROW64: the fixed-stride variant of the 16-lane kernel that stores state rows on the two-kernel path -- rows of RP_ROW64 doubles, no
+// split tail (17 <= N + 1 <= 64 with padded rows: the reference's default N = 60), known at compile time: the 14 rows of a step lie
+// at immediate offsets from ONE address per lane, and the split-tail code is gone.  The host takes it by the layout (rp_host.hip:
+// launch_eval_tcs); the layout in device memory is the generic variant's.
+#define RP_ROW64 64
+template <int G, bool MAT, bool COEFFS_IN, int COLL, bool ONE_CHUNK, bool STAGE_OUT, bool LON_FUSED, int BLOCK = RP_BLOCK, bool SWEEP = false,
+          bool ROW64 = false>
 __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const KArgsG ag) {
     static_assert(!SWEEP || (G == 16 && !MAT && COLL != 0 && !STAGE_OUT && !LON_FUSED && BLOCK == RP_BLOCK), "the sweep's variant");
+    static_assert(!ROW64 || (G == 16 && MAT && !ONE_CHUNK && !STAGE_OUT && !LON_FUSED && !SWEEP), "the fixed-stride variant");
     const KArgs &a = ag.k;
     extern __shared__ double lds_out[];   // STAGE_OUT: [groups per block][14][N+1];  LON_FUSED: tables, profiles, headers, votes
     static_assert(!(LON_FUSED && STAGE_OUT), "the single-launch variant stores state rows directly");
@@ -2192,6 +2201,27 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
         if (i == mid && al.has_speed) { e = v - al.desired_speed; cst += 100.0 * (e * e); }
         return cst;
     };
+    // The same terms from a block of the six cost parameters the caller has fetched (the fixed-stride variant: one fetch per step
+    // block).  The uniform tests on has_speed / has_s stay BRANCHES behind an empty asm: with the parameters in registers the compiler
+    // turns them into selects, i.e. every lane evaluates every term -- 53 more vector instructions per wavefront on cfg3, measured
+    // (profiles/r05_lean_block_ab.txt).  (Same reason as above for a lambda; touching eval_cost_terms itself -- a parameter for where
+    // it reads from -- changes the register allocation of every other variant.)
+    auto fetched_cost_terms = [&](const CostParams &cp, int i, double acc, double v, double s, double d, double th_cl) -> double {
+        double e, cst;
+        e = cp.w_a * acc; cst = e * e;
+        e = 0.25 * (cp.desired_d - d); cst = __builtin_fma(e, e, cst);
+        e = 0.25 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
+        if (cp.has_speed) { asm volatile(""); e = 5.0 * (v - cp.desired_speed); cst = __builtin_fma(e, e, cst); }
+        if (cp.has_s) { asm volatile(""); e = 0.25 * (cp.desired_s - s); cst = __builtin_fma(e, e, cst); }
+        if (i == N) {
+            e = 20.0 * (cp.desired_d - d); cst = __builtin_fma(e, e, cst);
+            e = 5.0 * fabs(th_cl); cst = __builtin_fma(e, e, cst);
+            if (cp.has_speed) { asm volatile(""); e = v - cp.desired_speed; cst += 50.0 * (e * e); }
+            if (cp.has_s) { asm volatile(""); e = 20.0 * (cp.desired_s - s); cst = __builtin_fma(e, e, cst); }
+        }
+        if (i == mid && cp.has_speed) { asm volatile(""); e = v - cp.desired_speed; cst += 100.0 * (e * e); }
+        return cst;
+    };
 
     // The grid covers the batch: every lane group evaluates exactly one candidate (no persistent loop -- a loop over
     // candidates costs ~40 VGPRs of hoisted invariants and look-ahead state, i.e. the third wavefront per SIMD).
@@ -2240,9 +2270,9 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
             // Rows stored directly lie row_stride doubles apart (N + 1 rounded up to whole 64-byte lines): a lane group's run of
             // G consecutive steps then starts on a line boundary and covers whole lines, which is what a write-through store
             // needs to reach memory as one full-line write (248-byte rows cost 1.28 x the bytes: profiles/r02_pmc_traffic.json).
-            const int ns = (MAT && !STAGE_OUT) ? al.row_stride : n;
+            const int ns = ROW64 ? RP_ROW64 : ((MAT && !STAGE_OUT) ? al.row_stride : n);
             // split tail (state_offset): only where 16 lanes store rows straight to memory on the two-kernel path
-            constexpr bool SPLIT_OK = MAT && !STAGE_OUT && !LON_FUSED && G == 16;
+            constexpr bool SPLIT_OK = MAT && !STAGE_OUT && !LON_FUSED && G == 16 && !ROW64;
             const int tail_m = SPLIT_OK ? al.tail_split : 0;
             const uint32_t cand8 = (uint32_t)state_block_doubles(ns, tail_m) * 8u;   // bytes of one candidate's block
             char *const obase = !MAT ? nullptr
@@ -2288,6 +2318,10 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                 // workgroup then fall out of step with their row stores), so that variant evaluates every block as before.  Reading only
                 // the near mask of the profile in such a block was tried on top: slower everywhere (cfg3 draw 103.8 us).
                 constexpr bool SKIP_EXTENDED = !(MAT && COLL == 0);
+                // LEAN (the fixed-stride variant): a lane is either valid or extended in a step block, so the cost terms and the pose's
+                // cell of the static grid are evaluated ONCE, behind the horizon extension, from whichever state the lane holds there --
+                // per lane exactly the value the two copies (valid steps here, extended steps below) add
+                constexpr bool LEAN = ROW64;
                 double d = 0.0, dd = 0.0, ddd = 0.0, th_cl = 0.0, th_gl = 0.0, cos_gl = 1.0, sin_gl = 0.0;
                 double kappa = 0.0, v = 0.0, acc = 0.0, kdot = 0.0, x = 0.0, y = 0.0;
                 uint64_t near_sta_cell = 0;
@@ -2381,13 +2415,13 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                             st_row<RP_WT, RP_NT>(row_at(off8, RP_KAPPA_DOT), kdot);
                             st_row<RP_WT, RP_NT>(row_at(off8, RP_THETA_CL), th_cl);
                         }
-                        cost_acc += eval_cost_terms(i, acc, v, s, d, th_cl);
+                        if (!LEAN) cost_acc += eval_cost_terms(i, acc, v, s, d, th_cl);
                     }
                     // static shapes: the pose's cell of the grid over them (static_grid_mask) is requested here for the valid steps,
                     // whose pose is final, and behind the extension for the extended ones -- and waited for IN FRONT of the row stores.
                     // Loads and stores share one in-order counter (vmcnt): a load that is waited for behind the write-through stores
                     // of the rows is waited for together with their acknowledgements from memory (6 000 cycles per step block, measured).
-                    if (COLL == 2 && live && alive && fail_step < 0 && ood_step < 0 && !collide && act)   // (= cell_wanted below)
+                    if (!LEAN && COLL == 2 && live && alive && fail_step < 0 && ood_step < 0 && !collide && act)   // (= cell_wanted below)
                         near_sta_cell = static_grid_mask(al.obs.grid, al.obs.gx0, al.obs.gy0, al.obs.ginv, al.obs.gnx, al.obs.gny,
                                                          x + al.wb_rear_axle * cos_gl, y + al.wb_rear_axle * sin_gl);
                 }
@@ -2433,7 +2467,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                         const double e_dd = o[12] + tk * 0.0;          // :319
                         const double e_s = o[7] + tk * o[10];          // :330
                         const double e_d = o[8] + tk * o[12];          // :331
-                        if (live) cost_acc += eval_cost_terms(i, o[4], vt, e_s, e_d, o[9]);
+                        if (!LEAN && live) cost_acc += eval_cost_terms(i, o[4], vt, e_s, e_d, o[9]);
                         if (LATE_STORE) {   // what the step block's store below writes for this lane
                             v = vt; acc = o[4]; kappa = o[5]; kdot = o[6];
                             s = e_s; d = e_d; th_cl = o[9];
@@ -2463,8 +2497,19 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                         cumy = group_bcast<G>(scy, G - 1);
                     }
                 }
+                if (LEAN) {   // (LATE_STORE: an extended lane holds its extended state in acc, v, s, d, th_cl by now; act implies live)
+                    static_assert(!LEAN || LATE_STORE, "the lanes' row values are the extended state behind the extension");
+                    // The six launch-uniform cost parameters in ONE fetch per step block -- neighbours in KArgs: two wide scalar loads and
+                    // one wait -- through a pointer laundered here, inside the loop.  Read where they are used (eval_cost_terms), each
+                    // costs a scalar load and a wait of its own behind its uniform branch; hoisted out of the loop they would be spilled
+                    // into vector lanes (profiles/r05_dead_ends.txt item 8).
+                    kargs_cptr ac = ap_late;
+                    asm volatile("" : "+s"(ac));
+                    const CostParams cp = {ac->w_a, ac->desired_speed, ac->desired_d, ac->desired_s, ac->has_speed, ac->has_s};
+                    if (live) cost_acc += fetched_cost_terms(cp, i, acc, v, s, d, th_cl);
+                }
                 if (COLL == 2) {
-                    if (cell_wanted && !act)
+                    if (cell_wanted && (LEAN || !act))
                         near_sta_cell = static_grid_mask(al.obs.grid, al.obs.gx0, al.obs.gy0, al.obs.ginv, al.obs.gnx, al.obs.gny,
                                                          x + al.wb_rear_axle * cos_gl, y + al.wb_rear_axle * sin_gl);
                     uint32_t c_lo = (uint32_t)near_sta_cell, c_hi = (uint32_t)(near_sta_cell >> 32);
@@ -2483,6 +2528,31 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                         };
                         pair_store(0, x, y); pair_store(1, th_gl, v); pair_store(2, acc, kappa); pair_store(3, kdot, s);
                         pair_store(4, d, th_cl); pair_store(5, sd, sdd); pair_store(6, dd, ddd);
+                    }
+                } else
+                if (ROW64) {   // (i < RP_ROW64 in every lane: the step blocks of N + 1 <= 64 steps end at 64)
+                    if (store_ok) {
+                        // row 7 of this lane's element: the 14 rows lie (row - 7) * 512 bytes from it, within the +-4 KB an immediate
+                        // offset of a store covers (the empty asm keeps the compiler from re-forming an address per row)
+                        char *mid_row = obase + (size_t)(lane_off8 + (uint32_t)i * 8u + 7u * (RP_ROW64 * 8u));
+                        asm volatile("" : "+v"(mid_row));
+                        // (named as global memory again: behind the asm the compiler no longer knows, and would store through flat addresses)
+                        typedef double __attribute__((address_space(1))) *grow;
+                        auto row64 = [&](int row) -> double * { return (double *)(grow)(uintptr_t)(mid_row + (row - 7) * (RP_ROW64 * 8)); };
+                        st_row<RP_WT, RP_NT>(row64(RP_X), x);
+                        st_row<RP_WT, RP_NT>(row64(RP_Y), y);
+                        st_row<RP_WT, RP_NT>(row64(RP_THETA), th_gl);
+                        st_row<RP_WT, RP_NT>(row64(RP_V), v);
+                        st_row<RP_WT, RP_NT>(row64(RP_A), acc);
+                        st_row<RP_WT, RP_NT>(row64(RP_KAPPA), kappa);
+                        st_row<RP_WT, RP_NT>(row64(RP_KAPPA_DOT), kdot);
+                        st_row<RP_WT, RP_NT>(row64(RP_S), s);
+                        st_row<RP_WT, RP_NT>(row64(RP_D), d);
+                        st_row<RP_WT, RP_NT>(row64(RP_THETA_CL), th_cl);
+                        st_row<RP_WT, RP_NT>(row64(RP_S_DOT), sd);
+                        st_row<RP_WT, RP_NT>(row64(RP_S_DDOT), sdd);
+                        st_row<RP_WT, RP_NT>(row64(RP_D_DOT), dd);
+                        st_row<RP_WT, RP_NT>(row64(RP_D_DDOT), ddd);
                     }
                 } else
                 if (LATE_STORE && store_ok && i < ns) {   // (whole 128-byte lines: completing only the 64-byte half that holds step N
