@@ -1,1 +1,2 @@
 from .trajectory_check import TrajectoryChecker, TrajectoryCheckResult  # noqa: F401
+from .ensemble_check import EnsembleChecker, EnsembleCheckResult  # noqa: F401
