@@ -63,6 +63,7 @@ struct Options {
     int fused_lon = 1;           // single-launch variant for small batches
     int fused_lon_blocks = -1;   // ... up to this many workgroups (-1: 4 per CU)
     int auto_materialize = 1;    // small batches whose winner rows are wanted write every candidate's rows
+    int shard_policy = 1;        // what decides the producer of a range's cost bits (lanes per candidate, single launch or two kernels): 1 the grid, 0 the range
     int stage_out = 1, row_padding = 1, row_align = 0, tail_split = 1;   // layout of the state rows in device memory
     int fixed_stride = 1;        // fixed-stride variant of the 16-lane kernel that stores state rows (rows of 64 doubles, no split tail): 1 = by layout, 0 never
     int table_window = 1;        // single-launch variant stages only the part of the reference tables a plan can touch
@@ -89,6 +90,7 @@ const OptionDesc kOptionTable[] = {
     {"fused_lon", &Options::fused_lon, "RP_AMD_NO_FUSED_LON", true, 0, 1},
     {"fused_lon_blocks", &Options::fused_lon_blocks, "RP_AMD_FUSED_LON_BLOCKS", false, -1, 1 << 20},
     {"auto_materialize", &Options::auto_materialize, "RP_AMD_NO_AUTO_MATERIALIZE", true, 0, 1},
+    {"shard_policy", &Options::shard_policy, "RP_AMD_SHARD_POLICY", false, 0, 1},
     {"stage_out", &Options::stage_out, "RP_AMD_NO_STAGE_OUT", true, 0, 1},
     {"row_padding", &Options::row_padding, "RP_AMD_NO_ROW_PADDING", true, 0, 1},
     {"row_align", &Options::row_align, "RP_AMD_ROW_ALIGN", false, 0, 16},
@@ -873,7 +875,13 @@ int run_lazy(rp_ctx *c, const KArgs &ka, bool cin, int G, const int &grid /* wor
 // The result block lands in pinned host memory straight from the kernels; one stream sync per plan.
 int pipeline_wait(rp_ctx *c, rp_result *result, double *best_states);
 // chain_last: the level is the last one of its chain (or a plan on its own): its epilogue reports whatever it found
-int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, bool want_rows, bool chain_last = true) {
+// basis_count >= 0 (grid plans under option "shard_policy" = 1): the candidates of the WHOLE grid the range is cut from, and
+// basis_mat, whether a plan of that whole grid would keep state rows.  The two choices that decide the bits of a cost -- lanes per
+// candidate (the order of the per-step sum) and single launch or two kernels (which kernel computes the profile rows) -- are made
+// from them, so that a candidate's cost does not depend on how the grid was cut into ranges; everything else (grid and workgroup
+// size, the costs-only kernels, the cost-ordered stage, whether THIS range keeps rows) is bit-neutral and stays by range.
+int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, bool want_rows, bool chain_last = true, int64_t basis_count = -1,
+                   bool basis_mat = false) {
     if (c->time_whole) c->plan_t0 = std::chrono::steady_clock::now();
     c->path_adaptive = false;
     double *const best_states = want_rows ? reinterpret_cast<double *>(c) : nullptr;   // (only its being non-null matters below)
@@ -883,7 +891,9 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
     ResultBlock *drb = reinterpret_cast<ResultBlock *>(c->d_result);
     ResultBlock *hrb_dev = reinterpret_cast<ResultBlock *>(c->h_result_dev);
     const int64_t count = ka.count;
-    int G = lanes_per_candidate(c, ka.N, count, mat);
+    const int64_t pcount = (basis_count >= 0 && count > 0) ? basis_count : count;   // (an empty range launches nothing: as before)
+    const bool pmat = (basis_count >= 0 && count > 0) ? basis_mat : mat;            // (pmat implies mat: a range is no larger than its grid)
+    int G = lanes_per_candidate(c, ka.N, pcount, pmat);
     // small batches: one launch computes the longitudinal profiles and evaluates (rp_eval_kernel<.., LON_FUSED>)
     int fused_pairs = 0;
     size_t fused_lds = 0;
@@ -895,7 +905,7 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
         if (c->last_G) G = c->last_G;
     } else {
         // (grouped explicit polynomials: the two-kernel path -- the single-launch prologue counts one pair per candidate there)
-        if (c->opt.fused_lon && !(cin && ka.pair_of)) fused_lds = fused_lon_lds(c, ka, count, G, cin, mat, &fused_pairs);
+        if (c->opt.fused_lon && !(cin && ka.pair_of)) fused_lds = fused_lon_lds(c, ka, pcount, G, cin, pmat, &fused_pairs);
     }
     ka.lds_pairs = fused_pairs;
     if (!skip_eval) {
@@ -1468,6 +1478,8 @@ int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (!c || !value) return RP_EINVAL;
     if (key && std::strcmp(key, "wait_fallbacks") == 0) { *value = c->wait_fallbacks; return RP_OK; }   // (read-only counter)
     if (key && std::strcmp(key, "last_fixed_stride") == 0) { *value = c->last_fixed_stride; return RP_OK; }   // (read-only: the last plan's batch)
+    if (key && std::strcmp(key, "last_lanes") == 0) { *value = c->last_G; return RP_OK; }                    // (read-only: ... its lanes per candidate)
+    if (key && std::strcmp(key, "last_single_launch") == 0) { *value = c->last_fused_lds != 0 ? 1 : 0; return RP_OK; }   // (read-only: ... single launch or two kernels)
     const OptionDesc *d = find_option(key);
     if (!d) return RP_EINVAL;
     *value = c->opt.*(d->field);
@@ -1922,11 +1934,14 @@ int plan_begin_impl(rp_ctx *c, const rp_params *p, const rp_cost *cost, const rp
     const int64_t count = cand_end - cand_begin;
     const int n = p->N + 1;
     bool mat = (p->flags & RP_FLAG_MATERIALIZE_ALL) != 0 || cost->kind == RP_COST_EXTERNAL;
+    bool mat_grid = mat;   // ... of a plan of the whole grid (pipeline_begin: basis_mat)
     // Small batches whose winner block is wanted: write every candidate's state rows anyway.  The alternative -- a
     // second launch that re-evaluates the winner -- costs 12.6 us on cfg2, the rows of 7 440 candidates 2-3 us.
     if (!mat && best_states && (size_t)count * RP_N_ARRAYS * (size_t)n * sizeof(double) <= kAutoMaterializeBytes &&
         c->opt.auto_materialize)
         mat = true;
+    if (!mat_grid && best_states && (size_t)total * RP_N_ARRAYS * (size_t)n * sizeof(double) <= kAutoMaterializeBytes && c->opt.auto_materialize)
+        mat_grid = true;
     HIP_TRY(c, hipSetDevice(c->device));
 
     // stage grids: [T | L | D | traj_len]
@@ -1981,7 +1996,7 @@ int plan_begin_impl(rp_ctx *c, const rp_params *p, const rp_cost *cost, const rp
     table_window(c, p, g, ka);
     c->have_last = false;
     if (lg) { ka.gate = lg->gate; ka.gate_seq = lg->seq; ka.gate_level = lg->level; }
-    rc = pipeline_begin(c, ka, mat, false, false, best_states != nullptr, lg ? lg->last : true);
+    rc = pipeline_begin(c, ka, mat, false, false, best_states != nullptr, lg ? lg->last : true, c->opt.shard_policy ? total : -1, mat_grid);
     if (rc != RP_OK) return rc;
     c->pending.mat = mat; c->pending.coeffs = false;
     return RP_OK;

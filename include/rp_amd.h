@@ -204,6 +204,13 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "fused_lon"         RP_AMD_NO_FUSED_LON         1 | 0: single-launch variant of small batches
  *   "fused_lon_blocks"  RP_AMD_FUSED_LON_BLOCKS     -1 (4 workgroups per CU) | largest grid that takes it
  *   "auto_materialize"  RP_AMD_NO_AUTO_MATERIALIZE  1 | 0: small batches whose winner rows are wanted write every candidate's rows
+ *   "shard_policy"      RP_AMD_SHARD_POLICY         1 | 0: what decides the PRODUCER of the cost bits of a range [cand_begin, cand_end) of a grid --
+ *                                                   lanes per candidate of rp_eval_kernel (the order of the per-step sum) and single launch or
+ *                                                   two kernels (which kernel computes the profile rows).  1 (default): the whole grid and the
+ *                                                   parameters, i.e. what a plan of all nT*nL*nD candidates chooses: a candidate's cost and the
+ *                                                   combined result of a sharded plan do not depend on how the grid was cut.  0: the range's own
+ *                                                   size (small shards may take a faster variant; two shards can then disagree in the last bit
+ *                                                   of equal costs).  A whole-grid plan chooses the same either way; rp_plan_coeffs is by batch.
  *   "stage_out", "row_padding", "row_align" (0 | 8 | 16), "tail_split"   RP_AMD_NO_STAGE_OUT, _NO_ROW_PADDING, _ROW_ALIGN, _NO_TAIL_SPLIT
  *   "fixed_stride"      RP_AMD_NO_FIXED_STRIDE      1 by layout | 0 never: fixed-stride variant of the 16-lane rp_eval_kernel that stores state
  *                                                   rows (rows of 64 doubles without a split tail: padded rows of 17 .. 64 steps)
@@ -214,6 +221,10 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "wait_fallbacks"    (read-only, rp_get_option) waits for a completion ticket that ended in the 200-ms fall-back: 0 unless a kernel
  *                       chain failed to hand its ticket over
  *   "last_fixed_stride" (read-only, rp_get_option) 1: the batch of the last plan was evaluated by the fixed-stride variant
+ *   "last_lanes"        (read-only, rp_get_option) 16 | 32 | 64: lanes per candidate the last plan chose for rp_eval_kernel
+ *   "last_single_launch" (read-only, rp_get_option) 1: the last plan took the single-launch variant, 0: rp_lon_kernel + evaluation kernel
+ *                       (the two together name the producer of the plan's cost bits; rp_select, rp_eval_one and the winner's
+ *                       re-evaluation follow them)
  * RP_EINVAL: unknown key or value out of range; RP_ESTATE: a plan is in flight. */
 int rp_set_option(rp_ctx *ctx, const char *key, int64_t value);
 int rp_get_option(const rp_ctx *ctx, const char *key, int64_t *value);

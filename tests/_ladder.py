@@ -51,6 +51,7 @@ class SceneSpec:
     D_lo: float = -3.0
     D_hi: float = 3.3
     a_max: float = None      # None: the vehicle's
+    n_steps: int = 20        # N of the plan (N + 1 steps)
 
     @property
     def n_candidates(self):
@@ -65,6 +66,8 @@ _GMIR = dict(nT=6, nLu=11, rL=3, nDu=24, rD=2, D_lo=-2.875, D_hi=2.875)   # 9 50
 
 # name -> parameters (filled in at the end of the module; tests/test_ladder_scenes.py asserts what the table is there for)
 SCENES = {}
+# scenes outside the table of the selection modules (build() finds them too): a longer horizon for the modules on sharded plans
+EXTRA_SCENES = {}
 
 
 @dataclasses.dataclass
@@ -95,7 +98,7 @@ class Scene:
 
 
 def build(name) -> Scene:
-    sp = SCENES[name]
+    sp = SCENES[name] if name in SCENES else EXTRA_SCENES[name]
     s = np.arange(0.0, 201.0, 1.0)
     z = np.zeros_like(s)
     T = np.array([2.0, 1.6] * (sp.nT // 2))
@@ -104,7 +107,7 @@ def build(name) -> Scene:
     veh = dict(W.VEHICLE2)
     if sp.a_max is not None:
         veh["a_max"] = sp.a_max
-    p = make_params(dt=DT, N=N_STEPS, factor=1, time_step0=0, low_vel_mode=False, lon_mode=0, flags=0, x0_lon=[10.0, 10.0, 0.0],
+    p = make_params(dt=DT, N=sp.n_steps, factor=1, time_step0=0, low_vel_mode=False, lon_mode=0, flags=0, x0_lon=[10.0, 10.0, 0.0],
                     x0_lat=[0.0, 0.0, 0.0], x0_orientation=0.0, **veh)
     inp = PlanInputs(p, make_cost(desired_speed=10.0), T, W.traj_len_of(T, DT), L, D)
     wall = ObstacleTables(static_obb=[[sp.x_near + 9.0, sp.off, 0.0, 9.0, sp.w]])
@@ -292,6 +295,12 @@ SCENES.update({
     "mirror_rank73": _scene(**_GMIR, w=0.5, off=-1.0),
     "mirror_rank721": _scene(**_GMIR, w=1.0, off=-1.0),
 })
+# -- N = 40 (41 steps: three step blocks of 16, two of 32, one of 64 lanes -- the horizons of 33 .. 64 steps have their own thresholds
+#    between the lanes per candidate): the small grid, the winner behind the first list
+EXTRA_SCENES.update({
+    "n40_g8": _scene(**_G8, w=0.4, n_steps=40),
+})
+N40 = "n40_g8"
 LARGEST = "g135_rank29808"
 FOLD_ALIAS = "fold_alias"
 MIRROR = ("mirror_rank73", "mirror_rank721")
