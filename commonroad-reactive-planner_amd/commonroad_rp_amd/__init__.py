@@ -1,2 +1,3 @@
 from .trajectory_check import TrajectoryChecker, TrajectoryCheckResult  # noqa: F401
 from .ensemble_check import EnsembleChecker, EnsembleCheckResult  # noqa: F401
+from .clearance import ClearanceQuery, ClearanceResult  # noqa: F401
