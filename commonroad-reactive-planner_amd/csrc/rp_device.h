@@ -321,6 +321,7 @@ struct ObsTables {
     double gx0, gy0, ginv;            // origin and 1 / cell size
     int32_t gnx, gny;
     int32_t n_sobb, n_tri, n_circ, n_dyn, n_steps, dyn_t0, n_clus, clus_per;   // clus_per: members per cluster (upper bound)
+    int32_t n_fold;                   // the last n_fold rows of `dyn` are static rectangles (rp_host.hip: fold_view; 0: none, the tables as uploaded)
     double dyn_rmax_all;              // largest bounding radius of any dynamic obstacle at any step (pose_collides: circle pre-test of a lane's mask)
 };
 // behind the seven planes of `dyn`: [n_dyn][n_steps][2] cx, cy interleaved (16-byte aligned), then [n_dyn] the largest r_bound of
@@ -666,5 +667,10 @@ __device__ __forceinline__ bool pose_collides(const ObsTables &ob, const Obb &eg
             }
         }
     }
+    // Static rectangles among the rows (a folded view, which has no other static shape: !STATIC): the walk over static shapes
+    // reports a hit for an ego centre that is NaN -- none of its separating-axis comparisons is true -- and so does this one, whose
+    // circle tests say "far" for it.  A scalar branch: the tables as uploaded execute nothing behind it (the callers let such a lane
+    // ask behind the same branch).
+    if (!STATIC && ob.n_fold > 0) hit |= want && (ego.cx != ego.cx || ego.cy != ego.cy);
     return hit;
 }

@@ -28,6 +28,7 @@
 #include "rp_frontend.h"
 #include "rp_corridor.h"
 #include "rp_pool.h"
+#include "rp_fold_static.h"
 
 namespace {
 
@@ -67,6 +68,7 @@ struct Options {
     int stage_out = 1, row_padding = 1, row_align = 0, tail_split = 1;   // layout of the state rows in device memory
     int fixed_stride = 1;        // fixed-stride variant of the 16-lane kernel that stores state rows (rows of 64 doubles, no split tail): 1 = by layout, 0 never
     int table_window = 1;        // single-launch variant stages only the part of the reference tables a plan can touch
+    int fold_static = -1;        // a few static rectangles checked as rows of the dynamic table (fold_view): -1 = by rule, 0 never, 1 whenever the tables allow it
     int fold_threshold = kFoldThreshold;
     int lon_publish = 1, inline_grids = 1, event_bracket = 0, winner_lanes_as_batch = 0, zero_copy = 1, coeff_groups = 1;
     int winner_skip_query = 1;   // the re-evaluation of a production-mode plan's winner (its state rows) runs without the collision query
@@ -97,6 +99,7 @@ const OptionDesc kOptionTable[] = {
     {"tail_split", &Options::tail_split, "RP_AMD_NO_TAIL_SPLIT", true, 0, 1},
     {"fixed_stride", &Options::fixed_stride, "RP_AMD_NO_FIXED_STRIDE", true, 0, 1},
     {"table_window", &Options::table_window, "RP_AMD_NO_TABLE_WINDOW", true, 0, 1},
+    {"fold_static", &Options::fold_static, "RP_AMD_FOLD_STATIC", false, -1, 1},
     {"fold_threshold", &Options::fold_threshold, "RP_AMD_FOLD_THRESHOLD", false, 1, 1 << 30},
     {"lon_publish", &Options::lon_publish, "RP_AMD_NO_LON_PUBLISH", true, 0, 1},
     {"inline_grids", &Options::inline_grids, "RP_AMD_NO_INLINE_GRIDS", true, 0, 1},
@@ -155,6 +158,13 @@ struct rp_ctx {
     std::vector<int32_t> h_clus_info;
     bool grid_valid = false;
     double grid_ego_r = 0.0;
+    // the static rectangles as rows of the dynamic table (rp_fold_static.h; fold_view): host copy of the dynamic table as uploaded,
+    // whether the tables of the last rp_set_obstacles may be folded at all, the folded table and the steps it covers from dyn_t0 on
+    std::vector<double> h_dyn;
+    int fold_refusal = rpfs::kNoRectangle;
+    double *d_fold = nullptr;
+    size_t fold_cap = 0;   // doubles allocated at d_fold (kept across rp_set_obstacles: a replanning loop rebuilds the table, not the allocation)
+    int fold_steps = 0;
     int32_t *d_clus_info = nullptr;
     ObsTables obs{};
 
@@ -188,6 +198,7 @@ struct rp_ctx {
     int collision_mode = RP_COLLISION_AUTO;   // rp_set_collision_path
     int last_kernel = 0;                   // rp_last_kernel: which kernel evaluated the last plan's batch (RP_KERNEL_*)
     int last_fixed_stride = 0;             // ... and whether that was rp_eval_kernel's fixed-stride variant (read-only option "last_fixed_stride")
+    int last_collision_level = 0;          // ... and the collision level of its kernels (collision_level; read-only option "last_collision_level")
     int last_lazy = 0;                     // 0: the last plan ran eager, 1: lazy, 2: lazy attempt + eager fallback (diagnostic, rp_last_path)
     double last_best_cost = 0.0;           // winner of the last collected plan (rp_count_collisions_before after a cost-ordered plan)
     int64_t last_best_index = -1;
@@ -1425,7 +1436,7 @@ void rp_destroy(rp_ctx *c) {
                      c->t_sum[2] / c->t_calls, c->t_sum[3] / c->t_calls);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *dev[] = {c->d_tables, c->d_sobb, c->d_tri, c->d_circ, c->d_dyn, c->d_clus, c->d_slot, c->d_grid, c->d_clus_info, c->d_stage, c->d_status, c->d_cost, c->d_user,
+    void *dev[] = {c->d_tables, c->d_sobb, c->d_tri, c->d_circ, c->d_dyn, c->d_clus, c->d_slot, c->d_grid, c->d_fold, c->d_clus_info, c->d_stage, c->d_status, c->d_cost, c->d_user,
                    c->d_states, c->d_compact, c->d_partials, c->d_result, c->d_single, c->d_profile, c->d_profile_one,
                    c->d_pair_hdr, c->d_pair_hdr_one, c->d_sel_scratch, c->d_lazy_ctl, c->d_lazy_lists, c->d_lazy_hist, c->d_lazy_states, c->d_gate, c->d_sweep};
     for (void *p : dev)
@@ -1478,6 +1489,8 @@ int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (!c || !value) return RP_EINVAL;
     if (key && std::strcmp(key, "wait_fallbacks") == 0) { *value = c->wait_fallbacks; return RP_OK; }   // (read-only counter)
     if (key && std::strcmp(key, "last_fixed_stride") == 0) { *value = c->last_fixed_stride; return RP_OK; }   // (read-only: the last plan's batch)
+    if (key && std::strcmp(key, "last_collision_level") == 0) { *value = c->last_collision_level; return RP_OK; }   // (read-only: ... 0 no query, 1 dynamic table only, 2 static shapes as well)
+    if (key && std::strcmp(key, "fold_static_steps") == 0) { *value = c->d_fold ? c->fold_steps : 0; return RP_OK; }   // (read-only: steps the folded table covers; 0: not built)
     if (key && std::strcmp(key, "last_lanes") == 0) { *value = c->last_G; return RP_OK; }                    // (read-only: ... its lanes per candidate)
     if (key && std::strcmp(key, "last_single_launch") == 0) { *value = c->last_fused_lds != 0 ? 1 : 0; return RP_OK; }   // (read-only: ... single launch or two kernels)
     const OptionDesc *d = find_option(key);
@@ -1645,6 +1658,93 @@ static int ensure_static_grid(rp_ctx *c, double ego_r) {
     return RP_OK;
 }
 
+// Static rectangles as rows of the dynamic table (rp_fold_static.h).  Every launch of a plan is derived from the KArgs filled here, so
+// this is the one place where a plan gets its view of the obstacle tables: the folded one -- no static shape, n_dyn + n_sobb
+// dynamic obstacles, collision level 1 for the profile kernel, the three evaluation kernels, sweeps, cost-ordered rounds and the
+// single-launch prologue alike -- or the tables as rp_set_obstacles left them.  rp_check_swept and everything else that reads c->obs
+// outside a plan keeps the unfolded tables.
+//
+// Decided from the tables, the option and the plan's parameters (time_step0, N, factor) alone, never from a range: the shards of one
+// grid, and every rank, decide alike ("producer by grid").
+//
+// Rule of option "fold_static" = -1: up to kFoldMaxRects rectangles NEXT TO A DYNAMIC TABLE ("fold_static" = 1 folds whatever the
+// other conditions allow, rectangles alone included).  Rectangles alone is ZAM_Over (cfg1: one rectangle, 729 candidates, single
+// launch): folded, its plans measured 0.4 us SLOWER (31.3 -> 31.7 us, five alternating processes) -- a launch-bound plan gains nothing
+// from the shorter query, and the COLL = 1 instance evaluates more per step than the grid lookup that finds nothing -- so the rule
+// leaves such tables alone.
+// Same-box A/B, draw mode, cfg3's grid with cfg3f's 51 dynamic obstacles plus k parked-vehicle rectangles 9 m beside the route,
+// unfolded -> folded (profiles/fold_static_ab.txt, probe_fold_static.py):
+//     k       evaluation kernel, us        whole step, us
+//     1       136.81 -> 133.35             176.00 -> 175.35
+//     2       137.20 -> 133.53             176.39 -> 175.14
+//     4       136.70 -> 134.11             175.96 -> 175.56
+//     8       137.51 -> 134.47             176.24 -> 176.69
+// (min - max of a variant over six rounds: 0.3 - 0.9 us).  The grid lookup costs the same for any k; a folded row is one more
+// obstacle in every (pair, step) test of the profile kernel and one more bit for the walks.  The kernel keeps its 3 us up to eight
+// rectangles, the step gives them back from four on: the rule folds up to four.  cfg3 itself (one rectangle, in the ego lane, 50
+// dynamic obstacles): kernel 100.55 -> 97.08 us, step 141.57 -> 138.28 us.
+//
+// The window: dynamic obstacles exist for steps [dyn_t0, dyn_t0 + n_steps), static shapes always, so the folded table covers
+// [dyn_t0, dyn_t0 + fold_steps) with the dynamic rows absent (NaN) beyond their own window, and fold_steps at least the last step
+// any plan has asked for.  A plan that reaches further regrows the table -- with headroom, behind a stream synchronise, before it
+// launches anything: the levels of an rp_plan_levels chain share one rp_params, so the first level sizes it for all of them.  A
+// plan with a step before dyn_t0 (or beyond rpfs::kMaxSteps) takes the unfolded tables.
+//
+// Non-finite poses.  For an ego rectangle whose centre is NaN the static walk reports a hit (static_grid_mask says "every cluster",
+// and every comparison of the separating-axis tests is false); the dynamic part of pose_collides reports none (its circle tests
+// are <=).  A lane with such a pose can still ask: a NaN in the reference's orientation table reaches the heading, hence the centre,
+// of a candidate that is inside the projection domain and passes every constraint check (their comparisons are false on NaN as
+// well).  The folded view therefore carries the number of folded rows (ObsTables::n_fold), and the COLL = 1 query reports the hit
+// for a NaN centre when that number is positive (rp_device.h: pose_collides; the callers let such a lane ask, behind a scalar branch
+// on n_fold as well: a plan on the tables as uploaded evaluates nothing of this).  A centre at
+// +-infinity collides with nothing on either path (outside the grid | farther than any radius).
+constexpr int kFoldMaxRects = 4;
+// steps of the folded table this plan needs; 0: the plan takes the tables as uploaded (no device work: the decision alone)
+static int fold_steps_for(const rp_ctx *c, const rp_params *p) {
+    if (c->opt.fold_static == 0 || c->fold_refusal != rpfs::kFoldOk) return 0;
+    if (c->opt.fold_static < 0 && (c->obs.n_sobb > kFoldMaxRects || c->obs.n_dyn <= 0 || c->obs.n_steps <= 0)) return 0;
+    return rpfs::steps_needed(p->time_step0, p->N, p->factor, c->obs.dyn_t0);
+}
+// (the grid over the static shapes belongs to the ego rectangle of the plan; fill_common copies its descriptor.  A plan that takes
+//  the folded view reads no grid: it is not built for it -- rp_check_swept does not use it either.)
+static int ensure_static_grid_for(rp_ctx *c, const rp_params *p) {
+    if (fold_steps_for(c, p) > 0) return RP_OK;
+    return ensure_static_grid(c, std::sqrt(0.25 * p->length * p->length + 0.25 * p->width * p->width));
+}
+static int fold_view(rp_ctx *c, const rp_params *p, KArgs &ka) {
+    c->last_collision_level = collision_level(ka);
+    const int need = fold_steps_for(c, p);
+    if (need <= 0) return RP_OK;
+    const int n_sobb = c->obs.n_sobb, n_dyn = c->obs.n_dyn, dyn_steps = n_dyn > 0 ? c->obs.n_steps : 0;
+    const int n = n_dyn + n_sobb;
+    if (need > c->fold_steps || !c->d_fold) {
+        const int steps = rpfs::steps_grown(c->d_fold ? c->fold_steps : 0, need, dyn_steps);
+        if (rpfs::table_doubles(n, steps) != dyn_table_doubles(n, steps) || rpfs::xy_offset(n, steps) != dyn_xy_offset(n, steps) ||
+            c->h_dyn.size() != dyn_table_doubles(n_dyn, c->obs.n_steps))
+            return fail(c, RP_EINVAL, "fold_static: internal error, the layout of the folded table does not match the kernels'");
+        std::vector<double> t(rpfs::table_doubles(n, steps));
+        rpfs::build(t.data(), n_dyn, dyn_steps, c->h_dyn.data(), n_sobb, c->h_sobb.data(), steps);
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));   // (a kernel of an earlier plan may still read the old table)
+        c->fold_steps = 0;
+        if (t.size() > c->fold_cap) {
+            if (c->d_fold) { HIP_TRY(c, hipFree(c->d_fold)); c->d_fold = nullptr; }
+            c->fold_cap = 0;
+            HIP_TRY(c, hipMalloc((void **)&c->d_fold, t.size() * sizeof(double)));
+            c->fold_cap = t.size();
+        }
+        HIP_TRY(c, hipMemcpy(c->d_fold, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+        c->fold_steps = steps;
+    }
+    ObsTables &o = ka.obs;
+    o.dyn = c->d_fold; o.n_dyn = n; o.n_steps = c->fold_steps; o.n_fold = n_sobb;
+    o.dyn_rmax_all = rpfs::folded_rmax_all(n_sobb, c->h_sobb.data(), n_dyn, c->obs.dyn_rmax_all);
+    o.n_sobb = 0; o.n_clus = 0; o.grid = nullptr; o.gnx = o.gny = 0;
+    ka.has_obstacles = 1;
+    c->last_collision_level = collision_level(ka);
+    return RP_OK;
+}
+
 int rp_set_obstacles(rp_ctx *c, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ,
                      const double *circ, int32_t n_dyn, int32_t n_steps, int32_t dyn_t0, const double *dyn) {
     if (!c) return RP_EINVAL;
@@ -1765,6 +1865,11 @@ int rp_set_obstacles(rp_ctx *c, int32_t n_sobb, const double *sobb, int32_t n_tr
     c->obs.n_dyn = n_dyn; c->obs.n_steps = n_steps; c->obs.dyn_t0 = dyn_t0; c->obs.dyn_rmax_all = rmax_all;
     c->obs.clus = c->d_clus; c->obs.clus_info = c->d_clus_info; c->obs.n_clus = n_clus; c->obs.clus_per = clus_per;
     c->obs.slot = c->d_slot;
+    // the folded view of these tables (fold_view) is built by the first plan that takes it
+    c->fold_steps = 0;
+    c->fold_refusal = rpfs::refusal(n_sobb, a.data(), n_tri, n_circ, n_dyn, rmax_all, rpfs::kMaxObstacles);
+    if (c->fold_refusal == rpfs::kFoldOk) c->h_dyn = e;   // (tables that cannot fold keep no host copy)
+    else c->h_dyn.clear();
     // (a replanning loop that brings new predictions of the dynamic obstacles every cycle keeps its static shapes: so does the grid)
     const bool same_static = c->grid_valid && a == c->h_sobb && b == c->h_tri && d == c->h_circ && ci == c->h_clus_info;
     if (!same_static) {
@@ -1972,11 +2077,12 @@ int plan_begin_impl(rp_ctx *c, const rp_params *p, const rp_cost *cost, const rp
     if (mat && (rc = grow(c, c->d_states, c->cap_states, (size_t)count * RP_N_ARRAYS * (size_t)((n + 15) & ~15))) != RP_OK) return rc;
 
     KArgs ka;
-    {   // (the grid over the static shapes belongs to the ego rectangle of the plan; fill_common copies its descriptor)
-        const int grc = ensure_static_grid(c, std::sqrt(0.25 * p->length * p->length + 0.25 * p->width * p->width));
+    {
+        const int grc = ensure_static_grid_for(c, p);
         if (grc != RP_OK) return grc;
     }
     fill_common(c, p, cost, ka);
+    if ((rc = fold_view(c, p, ka)) != RP_OK) return rc;
     const double *ds = reinterpret_cast<const double *>(c->d_stage);
     ka.nT = g->nT; ka.nL = g->nL; ka.nD = g->nD; ka.grids_inline = grids_inline ? 1 : 0;
     ka.T = ds; ka.L = ds + g->nT; ka.D = ds + g->nT + g->nL;
@@ -1992,7 +2098,7 @@ int plan_begin_impl(rp_ctx *c, const rp_params *p, const rp_cost *cost, const rp
     ka.lat_abs_d = std::max(std::fabs(p->x0_lat[0]), std::max(std::fabs(ka.lat_dmin), std::fabs(ka.lat_dmax)));
     // (NaN / inf samples: pair_step_bound reports "no bound" and the masks come out all ones.  The evaluation kernels of grid
     //  plans always take the masked query: use_near_mask only tells the profile kernels whether there is anything to mask.)
-    if (c->obs.n_dyn <= 0 && c->obs.n_clus == 0) ka.use_near_mask = 0;
+    if (ka.obs.n_dyn <= 0 && ka.obs.n_clus == 0) ka.use_near_mask = 0;
     table_window(c, p, g, ka);
     c->have_last = false;
     if (lg) { ka.gate = lg->gate; ka.gate_seq = lg->seq; ka.gate_level = lg->level; }
@@ -2259,11 +2365,12 @@ int rp_plan_coeffs(rp_ctx *c, const rp_params *p, const rp_cost *cost, int64_t C
     if ((rc = grow(c, c->d_cost, c->cap_cost, (size_t)C)) != RP_OK) return rc;
     if (mat && (rc = grow(c, c->d_states, c->cap_states, (size_t)C * RP_N_ARRAYS * (size_t)((n + 15) & ~15))) != RP_OK) return rc;
     KArgs ka;
-    {   // (the grid over the static shapes belongs to the ego rectangle of the plan; fill_common copies its descriptor)
-        const int grc = ensure_static_grid(c, std::sqrt(0.25 * p->length * p->length + 0.25 * p->width * p->width));
+    {
+        const int grc = ensure_static_grid_for(c, p);
         if (grc != RP_OK) return grc;
     }
     fill_common(c, p, cost, ka);
+    if ((rc = fold_view(c, p, ka)) != RP_OK) return rc;
     ka.lon_coeffs = d_lon; ka.lat_coeffs = d_lat;
     ka.traj_len_c = d_tl;
     ka.cand_begin = 0; ka.count = C;

@@ -2592,7 +2592,20 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     const uint64_t near_sta = want ? near_sta_cell : 0;
                     // (explicit polynomials have no (pair, step) masks of dynamic obstacles: those are all tested; static shapes go
                     //  through the grid for every kind of plan)
-                    const bool ask = want && ((!masked && al.obs.n_dyn > 0) || (near_dyn | near_sta) != 0);
+                    bool ask = want && ((!masked && al.obs.n_dyn > 0) || (near_dyn | near_sta) != 0);
+                    // Static rectangles folded into the dynamic table (ObsTables::n_fold, COLL == 1 only): a lane whose ego centre is
+                    // NaN asks as well -- it collides with them, pose_collides.  A scalar branch, kept one by the empty asm (the
+                    // compiler may not evaluate the comparisons ahead of it): plans on the tables as uploaded execute no vector
+                    // instruction of this.
+                    if (COLL == 1) {
+                        int n_fold = al.obs.n_fold;
+                        asm volatile("" : "+s"(n_fold));
+                        if (n_fold > 0) {
+                            double cx = ego_cx;
+                            asm volatile("" : "+v"(cx));
+                            ask |= want && (cx != cx || ego_cy != ego_cy);
+                        }
+                    }
                     RP_STAMP(44);
 #ifdef RP_WALK_COUNT
                     if (a.debug && !a.single_index && blockIdx.x == RP_STAMP_BLOCK && threadIdx.x == RP_STAMP_THREAD) rp_walk_dbg = a.debug + 40;
@@ -2603,7 +2616,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                         ob.clus = al.obs.clus; ob.clus_info = al.obs.clus_info;
                         ob.n_sobb = al.obs.n_sobb; ob.n_tri = al.obs.n_tri; ob.n_circ = al.obs.n_circ; ob.n_dyn = al.obs.n_dyn;
                         ob.n_steps = al.obs.n_steps; ob.dyn_t0 = al.obs.dyn_t0; ob.n_clus = al.obs.n_clus; ob.clus_per = al.obs.clus_per;
-                        ob.dyn_rmax_all = al.obs.dyn_rmax_all;
+                        ob.dyn_rmax_all = al.obs.dyn_rmax_all; ob.n_fold = al.obs.n_fold;
                         const Obb ego = {ego_cx, ego_cy, cos_gl, sin_gl, al.half_length, al.half_width};
                         RP_STAMP(45);
                         hit = pose_collides<masked, COLL == 2, LON_FUSED && COLL == 2, true, !MAT>(ob, ego, al.ego_radius, al.time_step0 + i * al.factor, ask,
@@ -2714,7 +2727,16 @@ __device__ __forceinline__ bool pose_query(const KArgs &a, const FLD &fld, bool 
     uint64_t near_sta = 0;
     if (COLL == 2 && want)
         near_sta = static_grid_mask(a.obs.grid, a.obs.gx0, a.obs.gy0, a.obs.ginv, a.obs.gnx, a.obs.gny, ego_cx, ego_cy);
-    const bool ask = want && (near_dyn | near_sta) != 0;
+    bool ask = want && (near_dyn | near_sta) != 0;
+    if (COLL == 1) {   // (folded static rectangles: a NaN ego centre asks as well, behind a scalar branch -- see rp_eval_kernel)
+        int n_fold = a.obs.n_fold;
+        asm volatile("" : "+s"(n_fold));
+        if (n_fold > 0) {
+            double cx = ego_cx;
+            asm volatile("" : "+v"(cx));
+            ask |= want && (cx != cx || ego_cy != ego_cy);
+        }
+    }
     if (__any(ask)) {   // wave-uniform; every lane runs the query code (wave-level culling inside)
         const Obb ego = {ego_cx, ego_cy, cs, sn, a.half_length, a.half_width};
         return pose_collides<true, COLL == 2, false, true>(a.obs, ego, a.ego_radius, a.time_step0 + i * a.factor, ask, near_dyn, near_sta) && ask;

@@ -215,12 +215,24 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "fixed_stride"      RP_AMD_NO_FIXED_STRIDE      1 by layout | 0 never: fixed-stride variant of the 16-lane rp_eval_kernel that stores state
  *                                                   rows (rows of 64 doubles without a split tail: padded rows of 17 .. 64 steps)
  *   "table_window", "lon_publish", "inline_grids", "zero_copy", "coeff_groups", "winner_skip_query"   RP_AMD_NO_<NAME>: 1 | 0
+ *   "fold_static"       RP_AMD_FOLD_STATIC          -1 by rule | 0 never | 1 whenever the tables allow it: a few static rectangles are checked as
+ *                                                   rows of the dynamic-obstacle table, so that the plan's kernels carry no static-shape
+ *                                                   query (collision level 1 instead of 2).  Folded only when the tables hold no triangle
+ *                                                   and no circle, dynamic obstacles + rectangles <= 63, no rectangle is larger than the
+ *                                                   largest dynamic obstacle (none: than the largest rectangle), every rectangle is finite,
+ *                                                   and the plan has no step before dyn_t0; by rule: at most 4 rectangles next to a dynamic
+ *                                                   table (rectangles alone fold with 1 only).  Results are
+ *                                                   the same either way; rp_check_swept always reads the tables as uploaded.
  *   "fold_threshold"    RP_AMD_FOLD_THRESHOLD       block partials beyond which they are folded before the epilogue
  *   "event_bracket", "winner_lanes_as_batch", "lazy_trace", "print_stamps", "timing"   RP_AMD_<NAME>: 0 | 1 (measurement variants, diagnostics on stderr)
  *   "wait_mode"         RP_AMD_WAIT_MODE            RP_WAIT_* (as rp_set_wait_mode)
  *   "wait_fallbacks"    (read-only, rp_get_option) waits for a completion ticket that ended in the 200-ms fall-back: 0 unless a kernel
  *                       chain failed to hand its ticket over
  *   "last_fixed_stride" (read-only, rp_get_option) 1: the batch of the last plan was evaluated by the fixed-stride variant
+ *   "last_collision_level" (read-only, rp_get_option) 0 | 1 | 2: the kernels of the last plan ran without a collision query | against the
+ *                       dynamic table only (also: static rectangles folded into it, "fold_static") | against static shapes as well
+ *   "fold_static_steps" (read-only, rp_get_option) time steps from dyn_t0 on that the folded table covers (0: not built); a plan that
+ *                       reaches further rebuilds it before it launches
  *   "last_lanes"        (read-only, rp_get_option) 16 | 32 | 64: lanes per candidate the last plan chose for rp_eval_kernel
  *   "last_single_launch" (read-only, rp_get_option) 1: the last plan took the single-launch variant, 0: rp_lon_kernel + evaluation kernel
  *                       (the two together name the producer of the plan's cost bits; rp_select, rp_eval_one and the winner's
