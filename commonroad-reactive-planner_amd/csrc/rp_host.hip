@@ -29,6 +29,7 @@
 #include "rp_corridor.h"
 #include "rp_pool.h"
 #include "rp_fold_static.h"
+#include "rp_table_window.h"
 
 namespace {
 
@@ -644,46 +645,17 @@ void fill_common(const rp_ctx *c, const rp_params *p, const rp_cost *cost, KArgs
     ka.ticket_if_none = 1;   // (gate == nullptr: a plan on its own)
 }
 
-// Part of the reference-table block a grid plan can touch (single-launch variant: every workgroup stages the block in
-// LDS -- 28 KB x 465 workgroups on cfg2 -- although one replanning cycle moves over a few dozen metres of a route of
-// hundreds).  s of every valid step lies between the bounds the Hermite form of the longitudinal polynomial gives:
-//   velocity keeping (quartic, v cubic from (v0, a0) to (vd, 0)):  v in [min(v0, vd) - c T |a0|, max(v0, vd) + c T |a0|], c = 4/27
-//   stopping (quintic to (sf, 0, 0)):  s in [min(s0, sf), max(s0, sf)] -+ (0.2 |v0| T + 0.0173 |a0| T^2)
-// An estimate, not a guarantee the kernel relies on: the kernel checks every item against [win_s_lo, win_s_hi) and stages
-// the whole block when one falls outside (steps beyond the end of the route, NaN samples, ...).
+// Part of the reference-table block a grid plan can touch: the rule is rp_table_window.h (rptw::table_window), here it meets the
+// context and the kernel arguments.
+static_assert(rptw::kLonStopping == RP_LON_STOPPING, "rp_table_window.h: kLonStopping is RP_LON_STOPPING");
 void table_window(const rp_ctx *c, const rp_params *p, const rp_grids *g, KArgs &ka) {
     ka.win_n = 0;   // whole block
-    const int n = c->n_ref;
-    if (n < 96 || c->n_buckets <= 0 || g->nT <= 0 || g->nL <= 0 || !c->opt.table_window) return;
-    double Tmax = g->T[0], Lmin = g->L[0], Lmax = g->L[0];
-    for (int i = 1; i < g->nT; ++i) Tmax = std::max(Tmax, g->T[i]);
-    for (int i = 1; i < g->nL; ++i) { Lmin = std::min(Lmin, g->L[i]); Lmax = std::max(Lmax, g->L[i]); }
-    const double s0 = p->x0_lon[0], v0 = p->x0_lon[1], a0 = std::fabs(p->x0_lon[2]);
-    double lo, hi;
-    if (p->lon_mode == RP_LON_STOPPING) {
-        const double over = 0.2 * std::fabs(v0) * Tmax + 0.0173 * a0 * Tmax * Tmax;
-        lo = std::min(s0, Lmin) - over; hi = std::max(s0, Lmax) + over;
-    } else {
-        const double dv = (4.0 / 27.0) * Tmax * a0;
-        lo = s0 + std::min(0.0, (std::min(v0, Lmin) - dv) * Tmax); hi = s0 + std::max(0.0, (std::max(v0, Lmax) + dv) * Tmax);
-    }
-    if (!(lo <= hi) || !(hi - lo < 1e300)) return;   // NaN / inf samples
-    const double *pos = c->h_pos.data();
-    const int seg_lo = (int)(std::upper_bound(pos, pos + n, lo) - pos) - 1, seg_hi = (int)(std::upper_bound(pos, pos + n, hi) - pos) - 1;
-    // an item in segment seg reads vertices seg - 2 .. seg + 3 (bucket fix-ups, both interpolation pairs)
-    int w0 = std::max(0, seg_lo - 3), w1 = std::min(n, seg_hi + 5);
-    int shift = 4;
-    while ((1 << shift) < w1 - w0) ++shift;
-    const int wn = 1 << shift;
-    if (wn * 2 > n || wn > 128) return;              // not worth a window | the kernel holds at most 5 pieces per lane
-    if (w0 + wn > n) w0 = n - wn;
-    ka.win_k0 = w0; ka.win_n = wn; ka.win_shift = shift;
-    ka.win_s_lo = w0 == 0 ? pos[0] : pos[w0 + 2];
-    ka.win_s_hi = w0 + wn == n ? pos[n - 1] : pos[w0 + wn - 4];
-    // bucket entries of [win_s_lo, win_s_hi): the kernel's index is (int)((s - pos[0]) * bucket_inv_h), clamped to n_buckets - 1
-    const int b0 = std::max(0, (int)((ka.win_s_lo - pos[0]) * c->bucket_inv_h) - 1);
-    const int b1 = std::min(c->n_buckets - 1, (int)((ka.win_s_hi - pos[0]) * c->bucket_inv_h) + 1);
-    ka.win_b0 = b0; ka.win_nb = b1 - b0 + 1;
+    if (!c->opt.table_window) return;
+    const rptw::Window w = rptw::table_window(c->h_pos.data(), c->n_ref, c->n_buckets, c->bucket_inv_h, p->lon_mode, p->x0_lon, g->T, g->nT, g->L, g->nL);
+    if (w.n == 0) return;
+    ka.win_k0 = w.k0; ka.win_n = w.n; ka.win_shift = w.shift;
+    ka.win_s_lo = w.s_lo; ka.win_s_hi = w.s_hi;
+    ka.win_b0 = w.b0; ka.win_nb = w.nb;
 }
 
 // the kernels' 28 words -> the caller's rp_result (its struct_size header stays the caller's)
@@ -1493,6 +1465,8 @@ int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (key && std::strcmp(key, "fold_static_steps") == 0) { *value = c->d_fold ? c->fold_steps : 0; return RP_OK; }   // (read-only: steps the folded table covers; 0: not built)
     if (key && std::strcmp(key, "last_lanes") == 0) { *value = c->last_G; return RP_OK; }                    // (read-only: ... its lanes per candidate)
     if (key && std::strcmp(key, "last_single_launch") == 0) { *value = c->last_fused_lds != 0 ? 1 : 0; return RP_OK; }   // (read-only: ... single launch or two kernels)
+    if (key && std::strcmp(key, "last_table_window") == 0) { *value = c->have_last ? c->last.win_n : 0; return RP_OK; }          // (read-only: ... vertices of its table window, 0: the whole block)
+    if (key && std::strcmp(key, "last_table_window_first") == 0) { *value = c->have_last ? c->last.win_k0 : 0; return RP_OK; }   // (read-only: ... the window's first vertex)
     const OptionDesc *d = find_option(key);
     if (!d) return RP_EINVAL;
     *value = c->opt.*(d->field);
@@ -1537,21 +1511,14 @@ int rp_set_reference(rp_ctx *c, int32_t n, const double *ref_pos, const double *
     }
     // reciprocal segment lengths; the last slot serves the wrap-around pair (k0 = n-1, k1 = 0)
     double *inv = &t[(size_t)TB_INVLEN * n];
-    double hmin = ref_pos[1] - ref_pos[0];
-    for (int i = 0; i + 1 < n; ++i) {
-        inv[i] = 1.0 / (ref_pos[i + 1] - ref_pos[i]);
-        hmin = std::min(hmin, ref_pos[i + 1] - ref_pos[i]);
-    }
+    for (int i = 0; i + 1 < n; ++i) inv[i] = 1.0 / (ref_pos[i + 1] - ref_pos[i]);
     inv[n - 1] = 1.0 / (ref_pos[0] - ref_pos[n - 1]);
-    // uniform bucket table for the O(1) segment lookup (falls back to binary search if too fine)
-    const double span = ref_pos[n - 1] - ref_pos[0];
-    const double nbf = std::floor(span / hmin) + 1.0;
-    int nb = (nbf >= 1.0 && nbf <= 8192.0) ? (int)nbf : 0;
+    // uniform bucket table for the O(1) segment lookup (falls back to binary search if too fine): rp_table_window.h
+    const double hmin = rptw::shortest_segment(ref_pos, n);
+    const int nb = rptw::bucket_count(ref_pos, n, hmin);
     if (nb > 0) {
         t.resize(t.size() + (size_t)(nb + 1) / 2, 0.0);
-        int32_t *bk = reinterpret_cast<int32_t *>(t.data() + (size_t)TB_ROWS * n);
-        for (int b = 0; b < nb; ++b)
-            bk[b] = (int32_t)(std::upper_bound(ref_pos, ref_pos + n, ref_pos[0] + b * hmin) - ref_pos);
+        rptw::bucket_fill(ref_pos, n, hmin, nb, reinterpret_cast<int32_t *>(t.data() + (size_t)TB_ROWS * n));
     }
     if (t.size() & 1) t.push_back(0.0);   // staged with 16-byte loads
     if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -237,6 +237,9 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "last_single_launch" (read-only, rp_get_option) 1: the last plan took the single-launch variant, 0: rp_lon_kernel + evaluation kernel
  *                       (the two together name the producer of the plan's cost bits; rp_select, rp_eval_one and the winner's
  *                       re-evaluation follow them)
+ *   "last_table_window" (read-only, rp_get_option) 16 | 32 | 64 | 128: vertices of the reference-table window in the last plan's kernel
+ *                       arguments ("table_window": the part of the tables the single-launch variant stages), 0: the whole block
+ *   "last_table_window_first" (read-only, rp_get_option) first vertex of that window (0 without one)
  * RP_EINVAL: unknown key or value out of range; RP_ESTATE: a plan is in flight. */
 int rp_set_option(rp_ctx *ctx, const char *key, int64_t value);
 int rp_get_option(const rp_ctx *ctx, const char *key, int64_t *value);

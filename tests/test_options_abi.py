@@ -43,6 +43,28 @@ def test_options_by_name(ctx_case):
     ctx.plan_wait()
 
 
+READ_ONLY_KEYS = ("wait_fallbacks", "last_fixed_stride", "last_collision_level", "fold_static_steps", "last_lanes", "last_single_launch",
+                  "last_table_window", "last_table_window_first")
+
+
+def test_read_only_keys(ctx_case):
+    """every read-only key of include/rp_amd.h: readable before and after a plan, refused by rp_set_option"""
+    ctx, g = ctx_case
+    before = {k: ctx.get_option(k) for k in READ_ONLY_KEYS}
+    assert before["last_table_window"] == 0 and before["last_table_window_first"] == 0 and before["last_single_launch"] == 0
+    ctx.plan(g.inputs)
+    after = {k: ctx.get_option(k) for k in READ_ONLY_KEYS}
+    assert after["last_single_launch"] == 1 and after["last_lanes"] in (16, 32, 64) and after["wait_fallbacks"] == 0
+    # the window of the plan's kernel arguments: the host rule's (tests/_window.py; tests/test_table_window_gpu.py has the scenes)
+    import _window
+    pos, p = np.asarray(g.z["ref_pos"], dtype=np.float64), g.inputs.params
+    w = _window.rule_window(pos, _window.bucket_table(pos), p.lon_mode, list(p.x0_lon), g.inputs.T, g.inputs.L)
+    assert (after["last_table_window"], after["last_table_window_first"]) == (w.n, w.k0)
+    for k in READ_ONLY_KEYS:
+        with pytest.raises(RpError, match="unknown option"):
+            ctx.set_option(k, 0)
+
+
 @pytest.mark.parametrize("mode", [_capi.WAIT_SPIN, _capi.WAIT_YIELD, _capi.WAIT_EVENT])
 def test_wait_modes_deliver_the_same_result(ctx_case, mode):
     ctx, g = ctx_case
