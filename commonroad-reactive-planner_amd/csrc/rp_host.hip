@@ -69,6 +69,7 @@ struct Options {
     int stage_out = 1, row_padding = 1, row_align = 0, tail_split = 1;   // layout of the state rows in device memory
     int fixed_stride = 1;        // fixed-stride variant of the 16-lane kernel that stores state rows (rows of 64 doubles, no split tail): 1 = by layout, 0 never
     int table_window = 1;        // single-launch variant stages only the part of the reference tables a plan can touch
+    int lean_broad = 1;          // rp_lon_kernel's LEAN instance (lean loop over the dynamic obstacles): 1 = whenever the table allows it, 0 never
     int fold_static = -1;        // a few static rectangles checked as rows of the dynamic table (fold_view): -1 = by rule, 0 never, 1 whenever the tables allow it
     int fold_threshold = kFoldThreshold;
     int lon_publish = 1, inline_grids = 1, event_bracket = 0, winner_lanes_as_batch = 0, zero_copy = 1, coeff_groups = 1;
@@ -100,6 +101,7 @@ const OptionDesc kOptionTable[] = {
     {"tail_split", &Options::tail_split, "RP_AMD_NO_TAIL_SPLIT", true, 0, 1},
     {"fixed_stride", &Options::fixed_stride, "RP_AMD_NO_FIXED_STRIDE", true, 0, 1},
     {"table_window", &Options::table_window, "RP_AMD_NO_TABLE_WINDOW", true, 0, 1},
+    {"lean_broad", &Options::lean_broad, "RP_AMD_NO_LEAN_BROAD", true, 0, 1},
     {"fold_static", &Options::fold_static, "RP_AMD_FOLD_STATIC", false, -1, 1},
     {"fold_threshold", &Options::fold_threshold, "RP_AMD_FOLD_THRESHOLD", false, 1, 1 << 30},
     {"lon_publish", &Options::lon_publish, "RP_AMD_NO_LON_PUBLISH", true, 0, 1},
@@ -199,6 +201,10 @@ struct rp_ctx {
     int collision_mode = RP_COLLISION_AUTO;   // rp_set_collision_path
     int last_kernel = 0;                   // rp_last_kernel: which kernel evaluated the last plan's batch (RP_KERNEL_*)
     int last_fixed_stride = 0;             // ... and whether that was rp_eval_kernel's fixed-stride variant (read-only option "last_fixed_stride")
+#ifdef RP_TIMELINE_LON
+    int last_lon_grid = 0;                 // diagnostic build: workgroups of the last rp_lon_kernel launch (their timeline is printed)
+#endif
+    int last_lon_lean = 0;                 // ... and whether its profile launch was rp_lon_kernel's LEAN instance (read-only option "last_lon_lean"; 0 also: no such launch)
     int last_collision_level = 0;          // ... and the collision level of its kernels (collision_level; read-only option "last_collision_level")
     int last_lazy = 0;                     // 0: the last plan ran eager, 1: lazy, 2: lazy attempt + eager fallback (diagnostic, rp_last_path)
     double last_best_cost = 0.0;           // winner of the last collected plan (rp_count_collisions_before after a cost-ordered plan)
@@ -581,14 +587,24 @@ int eval_block(const rp_ctx *c, const KArgs &ka, int64_t count, int G, bool mat)
     return (!mat && count > (int64_t)kFoldThreshold * (RP_BLOCK / 16)) ? 64 : RP_BLOCK;
 }
 
+// rp_lon_kernel's LEAN instance (option "lean_broad") reaches an obstacle's centre by a 32-bit byte offset per lane from a wave-uniform
+// row address: only for dynamic tables -- as the launch sees them, folded rows included -- that end below 4 GiB (every table of the
+// shipped configurations is a few hundred KiB; a larger one takes the kernel as it was)
+bool lon_lean_applies(const rp_ctx *c, const KArgs &ka) {
+    if (!c->opt.lean_broad) return false;
+    if (ka.obs.n_dyn <= 0 || ka.obs.n_steps <= 0) return true;
+    return (unsigned long long)dyn_table_doubles(ka.obs.n_dyn, ka.obs.n_steps) * 8ull < (1ull << 32);
+}
+
 template <int G, bool CIN>
 void launch_lon_t(rp_ctx *c, const KArgs &ka, int grid) {
     const size_t tbytes = (size_t)ka.table_words * sizeof(double);
     c->kargs_gl.k = ka;   // (the grid part is filled by rp_plan / run_pipeline and stays until the next plan: rp_eval_one)
-    if (tbytes <= kLdsTableLimit)
-        launch_block(c, (const void *)rp_lon_kernel<G, CIN, true>, grid, RP_BLOCK, tbytes, &c->kargs_gl, sizeof(KArgsGL));
-    else
-        launch_block(c, (const void *)rp_lon_kernel<G, CIN, false>, grid, RP_BLOCK, 0, &c->kargs_gl, sizeof(KArgsGL));
+    const bool lds = tbytes <= kLdsTableLimit;
+    const void *fn = lon_lean_applies(c, ka)
+        ? (lds ? (const void *)rp_lon_kernel<G, CIN, true, true> : (const void *)rp_lon_kernel<G, CIN, false, true>)
+        : (lds ? (const void *)rp_lon_kernel<G, CIN, true, false> : (const void *)rp_lon_kernel<G, CIN, false, false>);
+    launch_block(c, fn, grid, RP_BLOCK, lds ? tbytes : 0, &c->kargs_gl, sizeof(KArgsGL));
 }
 
 // longitudinal profiles of the pairs [ka.pair_begin, ka.pair_begin + ka.pair_count)
@@ -597,6 +613,9 @@ void launch_lon(rp_ctx *c, const KArgs &ka, bool cin) {
     const int G = (ka.N + 1 <= 32) ? 32 : 64;
     const int gpb = RP_BLOCK / G;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ka.pair_count + gpb - 1) / gpb, (int64_t)c->num_cus * kBlocksPerCU));
+#ifdef RP_TIMELINE_LON
+    c->last_lon_grid = grid;
+#endif
     if (G == 32) { if (cin) launch_lon_t<32, true>(c, ka, grid); else launch_lon_t<32, false>(c, ka, grid); }
     else         { if (cin) launch_lon_t<64, true>(c, ka, grid); else launch_lon_t<64, false>(c, ka, grid); }
 }
@@ -956,6 +975,7 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             c->staged_on_device = true;
         }
         // longitudinal profiles of every (T, longitudinal sample) pair touched by the candidate range
+        c->last_lon_lean = 0;
         if (count > 0 && !fused_lds) {
             if (cin) { ka.pair_begin = 0; ka.pair_count = ka.pair_of ? c->cin_groups : count; }
             else {
@@ -970,6 +990,7 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             kl.grids_inline = lon_inline ? 1 : 0;
             kl.publish_grids = lon_publish ? 1 : 0;
             launch_lon(c, kl, cin);
+            c->last_lon_lean = lon_lean_applies(c, kl) ? 1 : 0;   // (as launch_lon_t decides)
         }
         // the evaluation kernel's duration: events attached to the launch itself (hipExtModuleLaunchKernel; RP_AMD_EVENT_BRACKET=1:
         // two hipEventRecord around it, which adds the dispatch and completion handling of the bracket -- ~2.5 us on a 14-us kernel)
@@ -1289,7 +1310,11 @@ int pipeline_wait(rp_ctx *c, rp_result *result, double *best_states) {
         std::vector<unsigned long long> tl(2 * 4096);
         HIP_TRY(c, hipMemcpy(tl.data(), c->d_debug + 32, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull, t1 = 0;
+#ifdef RP_TIMELINE_LON
+        const int nb = std::max(1, std::min(c->last_lon_grid, 4096));   // (the workgroups of rp_lon_kernel were stamped: rp_kernels.h RP_TLL)
+#else
         const int nb = std::min(grid, 4096);
+#endif
         for (int b = 0; b < nb; ++b) { t0 = std::min(t0, tl[2 * b]); t1 = std::max(t1, tl[2 * b + 1]); }
         std::vector<unsigned long long> st(nb), en(nb), du(nb);
         for (int b = 0; b < nb; ++b) { st[b] = tl[2 * b] - t0; en[b] = tl[2 * b + 1] - t0; du[b] = tl[2 * b + 1] - tl[2 * b]; }
@@ -1297,7 +1322,7 @@ int pipeline_wait(rp_ctx *c, rp_result *result, double *best_states) {
         auto q = [&](const std::vector<unsigned long long> &v, double f) { return 0.01 * (double)v[(size_t)(f * (nb - 1))]; };
         std::fprintf(stderr, "timeline (us, 100 MHz clock): %d blocks, first start -> last end %.2f; starts p0/p25/p50/p55/p60/p75/p100 "
                      "%.2f %.2f %.2f %.2f %.2f %.2f %.2f; ends p0/p50/p100 %.2f %.2f %.2f; durations p0/p50/p100 %.2f %.2f %.2f\n",
-                     grid, 0.01 * (double)(t1 - t0), q(st, 0), q(st, .25), q(st, .5), q(st, .55), q(st, .6), q(st, .75), q(st, 1), q(en, 0), q(en, .5),
+                     nb, 0.01 * (double)(t1 - t0), q(st, 0), q(st, .25), q(st, .5), q(st, .55), q(st, .6), q(st, .75), q(st, 1), q(en, 0), q(en, .5),
                      q(en, 1), q(du, 0), q(du, .5), q(du, 1));
     }
 #endif
@@ -1461,6 +1486,7 @@ int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (!c || !value) return RP_EINVAL;
     if (key && std::strcmp(key, "wait_fallbacks") == 0) { *value = c->wait_fallbacks; return RP_OK; }   // (read-only counter)
     if (key && std::strcmp(key, "last_fixed_stride") == 0) { *value = c->last_fixed_stride; return RP_OK; }   // (read-only: the last plan's batch)
+    if (key && std::strcmp(key, "last_lon_lean") == 0) { *value = c->last_lon_lean; return RP_OK; }           // (read-only: ... its profile launch was rp_lon_kernel's LEAN instance)
     if (key && std::strcmp(key, "last_collision_level") == 0) { *value = c->last_collision_level; return RP_OK; }   // (read-only: ... 0 no query, 1 dynamic table only, 2 static shapes as well)
     if (key && std::strcmp(key, "fold_static_steps") == 0) { *value = c->d_fold ? c->fold_steps : 0; return RP_OK; }   // (read-only: steps the folded table covers; 0: not built)
     if (key && std::strcmp(key, "last_lanes") == 0) { *value = c->last_G; return RP_OK; }                    // (read-only: ... its lanes per candidate)

@@ -282,9 +282,10 @@ static_assert(sizeof(ResultCore) == 28 * 8 && sizeof(rp_result) == 8 + sizeof(Re
 #define RP_STAMP(k) do { } while (0)
 #endif
 // Per-block timeline (diagnostic build -DRP_TIMELINE): start / end of every workgroup on the 100 MHz constant clock
-// (s_memrealtime: the same counter on every XCD, unlike s_memtime).
+// (s_memrealtime: the same counter on every XCD, unlike s_memtime).  With -DRP_TIMELINE_LON besides, the workgroups of rp_lon_kernel
+// are stamped (RP_TLL) instead of the evaluation kernel's: the two share the slots.
 #ifdef RP_TIMELINE
-#define RP_TL(slot)                                                                               \
+#define RP_TL_STAMP(slot)                                                                         \
     do {                                                                                          \
         if (a.debug && !a.single_index && threadIdx.x == 0) {                                     \
             unsigned long long t_;                                                                \
@@ -292,8 +293,16 @@ static_assert(sizeof(ResultCore) == 28 * 8 && sizeof(rp_result) == 8 + sizeof(Re
             a.debug[32 + 2 * blockIdx.x + (slot)] = t_;                                           \
         }                                                                                         \
     } while (0)
+#endif
+#if defined(RP_TIMELINE) && !defined(RP_TIMELINE_LON)
+#define RP_TL(slot) RP_TL_STAMP(slot)
 #else
 #define RP_TL(slot) do { } while (0)
+#endif
+#if defined(RP_TIMELINE) && defined(RP_TIMELINE_LON)
+#define RP_TLL(slot) RP_TL_STAMP(slot)
+#else
+#define RP_TLL(slot) do { } while (0)
 #endif
 
 // stamps of rp_lon_kernel (diagnostic build -DRP_STAMPS without -DRP_TIMELINE: slots 32 .. of the debug buffer; one wavefront)
@@ -1517,7 +1526,83 @@ __device__ __forceinline__ bool static_shape_near(const ObsTables &ob, int kind,
 #ifndef RP_LON_BROAD_BATCH
 #define RP_LON_BROAD_BATCH 8
 #endif
-template <bool COEFFS_IN>
+// LEAN loop over the dynamic obstacles: the same tests, the same bits, about half the instructions per obstacle.  Against the loop
+// below it
+//   - addresses the centre of obstacle j at this lane's step k as wave-uniform base + 32-bit lane offset j * n_steps * 16 + k * 16,
+//     formed once and advanced by one 32-bit add per obstacle, instead of the 64-bit product (size_t)j * n_steps and a 64-bit lane
+//     address (the host takes this instance only for tables below 4 GiB: lon_lean_applies);
+//   - runs full batches without the tail clamp `j0 + u < n_dyn ? .. : n_dyn - 1`, fetches their kB radii as one run of scalar
+//     loads behind one wait, collects their kB result bits in a 32-bit register and shifts them into the mask once;
+//   - knows where the clamp `j < 63 ? j : 63` bites: never in a batch that ends at or before obstacle 63 (bit j is bit j0 + u), for
+//     every obstacle of a batch that begins at 64 or later (any hit is bit 63) -- kB divides 64, no batch straddles; the batches
+//     from 64 on have a loop of their own;
+//   - guards the tail batch's obstacles by wave-uniform branches instead of repeating the last obstacle.
+// The test itself is the contraction the compiler chose for the loop below, pinned: dy * dy, then fma(dx, dx, .).
+typedef const char __attribute__((address_space(4))) *gcchar;
+
+// one obstacle's test: the contraction the compiler chose for the loop of near_mask_step, pinned (dy * dy, then fma(dx, dx, .))
+__device__ __forceinline__ uint32_t lean_near(double ox, double oy, double r, double cx, double cy, double R) {
+    const double dx = ox - cx, dy = oy - cy, rr = R + r;   // NaN centre: absent, no bit
+    return (uint32_t)(__builtin_fma(dx, dx, dy * dy) <= rr * rr * 1.000001);
+}
+
+// a full batch: obstacles j0 .. j0 + kB - 1.  OVER: j0 >= 64, every hit is bit 63
+template <int kB, bool OVER>
+__device__ __forceinline__ uint64_t lean_full_batch(gcchar xy, uint32_t &voff, uint32_t stride, gcdouble rmax, int j0, double cx, double cy, double R) {
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    typedef const dbl2 __attribute__((address_space(4))) *gcdouble2;
+    dbl2 oc[kB];
+    double r[kB];
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+        oc[u] = *(gcdouble2)(xy + (uint64_t)voff);
+        voff += stride;
+    }
+#pragma unroll
+    for (int u = 0; u < kB; ++u) r[u] = rmax[j0 + u];
+    uint32_t bits = 0;
+#pragma unroll
+    for (int u = 0; u < kB; ++u) bits |= lean_near(oc[u].x, oc[u].y, r[u], cx, cy, R) << u;
+    return OVER ? (uint64_t)(bits != 0) << 63 : (uint64_t)bits << j0;
+}
+
+template <int kB>
+__device__ __forceinline__ uint64_t near_mask_dyn_lean(const ObsTables &ob, uint32_t k, double cx, double cy, double R) {
+    static_assert(kB >= 1 && kB <= 32 && 64 % kB == 0, "no batch straddles obstacle 63 / 64");
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    typedef const dbl2 __attribute__((address_space(4))) *gcdouble2;
+    const gcdouble dyn = (gcdouble)ob.dyn;
+    const int n_dyn = ob.n_dyn;
+    const gcdouble rmax = dyn + dyn_rmax_offset(n_dyn, ob.n_steps);
+    const gcchar xy = (gcchar)(dyn + dyn_xy_offset(n_dyn, ob.n_steps));   // centres of obstacle 0, step 0 (wave-uniform)
+    const uint32_t stride = (uint32_t)ob.n_steps * 16u;                   // bytes from an obstacle's centres to the next one's
+    uint32_t voff = k * 16u;                                              // obstacle j0 at this lane's step: j0 * stride + k * 16
+    uint64_t m = 0;
+    int j0 = 0;
+    const int n_low = n_dyn < 64 ? n_dyn : 64;
+    for (; j0 + kB <= n_low; j0 += kB) m |= lean_full_batch<kB, false>(xy, voff, stride, rmax, j0, cx, cy, R);
+    for (; j0 + kB <= n_dyn; j0 += kB) m |= lean_full_batch<kB, true>(xy, voff, stride, rmax, j0, cx, cy, R);
+    const int nt = n_dyn - j0;   // tail: 0 .. kB - 1 obstacles, each behind a wave-uniform branch
+    if (nt > 0) {
+        dbl2 oc[kB];
+        double r[kB];
+#pragma unroll
+        for (int u = 0; u < kB - 1; ++u)
+            if (u < nt) {
+                oc[u] = *(gcdouble2)(xy + (uint64_t)voff);
+                r[u] = rmax[j0 + u];
+                voff += stride;
+            }
+        uint32_t bits = 0;
+#pragma unroll
+        for (int u = 0; u < kB - 1; ++u)
+            if (u < nt) bits |= lean_near(oc[u].x, oc[u].y, r[u], cx, cy, R) << u;
+        m |= j0 < 64 ? (uint64_t)bits << j0 : (uint64_t)(bits != 0) << 63;
+    }
+    return m;
+}
+
+template <bool COEFFS_IN, bool LEAN = false>
 __device__ __forceinline__ void near_mask_step(const KArgs &a, const RefTab &rt, const LonPair &lp, int i, double *f,
                                                const double *last = nullptr) {
     f[PF_NEAR] = f[PF_NEAR_S] = mask_as_double(0);
@@ -1538,7 +1623,9 @@ __device__ __forceinline__ void near_mask_step(const KArgs &a, const RefTab &rt,
     const int k = a.time_step0 + i * a.factor - ob.dyn_t0;
     if (ob.n_dyn > 0 && k >= 0 && k < ob.n_steps) {   // (outside: no dynamic obstacle exists at this scenario step)
         uint64_t m = ~0ull;
-        if (bounded) {
+        if (bounded && LEAN) {
+            m = near_mask_dyn_lean<RP_LON_BROAD_BATCH>(ob, (uint32_t)k, cx, cy, R);
+        } else if (bounded) {
             const gcdouble dyn = (gcdouble)ob.dyn;
             m = 0;
             // One 16-byte load per obstacle (its centre at this step; dyn_xy_offset) and its radius as a scalar (the obstacle's largest
@@ -1595,7 +1682,10 @@ __device__ __forceinline__ void copy16_to_lds(const double *src, double *dst_lds
 
 // One group of G lanes per (T, longitudinal sample) pair, lane = time step: the profile is written once
 // and shared by the nD candidates of the pair (the reference recomputes it nD times).
-template <int G, bool COEFFS_IN, bool LDS_TABLES>
+// LEAN: the lean loop over the dynamic obstacles (near_mask_dyn_lean); LEAN = false is the kernel as it was (option "lean_broad" = 0).
+// (Requesting the first pair's inputs ahead of the table copy was tried with it and lost: the copy's first LDS store then waits for
+// those loads from the cold launch block, profiles/lon_lean_ab.txt 5.)
+template <int G, bool COEFFS_IN, bool LDS_TABLES, bool LEAN = false>
 #ifndef RP_LON_WAVES
 #define RP_LON_WAVES 1
 #endif
@@ -1605,6 +1695,7 @@ __global__ __launch_bounds__(RP_BLOCK, RP_LON_WAVES) void rp_lon_kernel(const KA
     RP_LSTAMP(0);
     touch_kernargs<10>();
     RP_LSTAMP(1);
+    RP_TLL(0);
     if (level_gate_closed(a.gate, a.gate_seq, a.gate_level)) return;   // (uniform) an earlier level of the chain has delivered
     const int tid = threadIdx.x;
     const int n_ref = a.n_ref;
@@ -1662,7 +1753,7 @@ __global__ __launch_bounds__(RP_BLOCK, RP_LON_WAVES) void rp_lon_kernel(const KA
                 last[PF_COS_REF] = group_bcast<G>(f[PF_COS_REF], src); last[PF_SIN_REF] = group_bcast<G>(f[PF_SIN_REF], src);
                 last[PF_INV_SD] = group_bcast<G>(f[PF_INV_SD], src);
             }
-            if (i <= N) near_mask_step<COEFFS_IN>(a, rt, lp, i, f, (masks && L >= 1) ? last : nullptr);
+            if (i <= N) near_mask_step<COEFFS_IN, LEAN>(a, rt, lp, i, f, (masks && L >= 1) ? last : nullptr);
             else f[PF_NEAR] = f[PF_NEAR_S] = 0.0;
             RP_LSTAMP(6);
             bad_a |= (i < L) && (fabs(f[PF_SDD]) > a.a_max);   // pre-filter, :798
@@ -1685,6 +1776,7 @@ __global__ __launch_bounds__(RP_BLOCK, RP_LON_WAVES) void rp_lon_kernel(const KA
         }
         RP_LSTAMP(8);
     }
+    RP_TLL(1);
 }
 
 // Store of one state-row element.  WT (single-launch variant): agent-scope write-through store.  The rows of a small

@@ -223,12 +223,18 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *                                                   and the plan has no step before dyn_t0; by rule: at most 4 rectangles next to a dynamic
  *                                                   table (rectangles alone fold with 1 only).  Results are
  *                                                   the same either way; rp_check_swept always reads the tables as uploaded.
+ *   "lean_broad"        RP_AMD_NO_LEAN_BROAD        1 | 0: rp_lon_kernel (the profile launch of the two-kernel path) runs its lean loop over the
+ *                                                   dynamic obstacles -- one scalar row address per obstacle, a batch's radii and result bits
+ *                                                   handled together -- whenever the dynamic table ends below 4 GiB.  The masks, and with them
+ *                                                   every result, are the same bits either way.
  *   "fold_threshold"    RP_AMD_FOLD_THRESHOLD       block partials beyond which they are folded before the epilogue
  *   "event_bracket", "winner_lanes_as_batch", "lazy_trace", "print_stamps", "timing"   RP_AMD_<NAME>: 0 | 1 (measurement variants, diagnostics on stderr)
  *   "wait_mode"         RP_AMD_WAIT_MODE            RP_WAIT_* (as rp_set_wait_mode)
  *   "wait_fallbacks"    (read-only, rp_get_option) waits for a completion ticket that ended in the 200-ms fall-back: 0 unless a kernel
  *                       chain failed to hand its ticket over
  *   "last_fixed_stride" (read-only, rp_get_option) 1: the batch of the last plan was evaluated by the fixed-stride variant
+ *   "last_lon_lean"     (read-only, rp_get_option) 1: the profile launch of the last plan was rp_lon_kernel's lean instance ("lean_broad"),
+ *                       0: the other one, or the plan had no such launch (single-launch variant)
  *   "last_collision_level" (read-only, rp_get_option) 0 | 1 | 2: the kernels of the last plan ran without a collision query | against the
  *                       dynamic table only (also: static rectangles folded into it, "fold_static") | against static shapes as well
  *   "fold_static_steps" (read-only, rp_get_option) time steps from dyn_t0 on that the folded table covers (0: not built); a plan that
