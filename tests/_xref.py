@@ -1,0 +1,774 @@
+"""Extended-precision reference of one candidate's evaluation (TEST INFRASTRUCTURE: tests/test_xref_abi.py on the CPU, tests/test_xref.py
+on the GPU).  A NumPy ``longdouble`` (x87, 64-bit significand; worked out in double-word arithmetic on it, tests/_dd.py, and rounded: rows that
+are differences of nearly equal numbers are then correct to the last bit as well) restatement of oracle/numpy_loop.py -- sample, polynomial rows, low-velocity
+lateral form, EPS clamps, per-step conversion, (s, d) -> (x, y) with the vertex tangents recomputed in longdouble from the double tables,
+kappa_dot, horizon extension with its zero-padding quirk, the two default cost functions with a plain sum -- vectorised over candidates.
+
+TRUTH here is: the reference's formulas evaluated exactly on the DOUBLE inputs.  The constants the reference holds as doubles stay those
+doubles (2 pi and pi of make_valid_orientation, 1e-5, 0.001).  States and costs only: labels, reasons and failing steps are compared
+exactly with the oracle elsewhere.
+
+The comparison (compare_rows, compare_costs) takes no number from the device: with X the reference, O the double oracle and D a device
+result, per case and row r over the compared elements (candidate x step)
+
+    E_D[r] <= 8 E_O[r] + 8 spacing(scale[r])        E = max |. - X|,  scale = max |X|
+    R_D[r] <= 4 R_O[r] + 2 spacing(scale[r])        R = root mean square of the same differences
+
+The oracle's primitive operations are correctly rounded (0.5 ulp) or libm's (<= 1 ulp); the device's documented bounds
+(tests/test_gpu_math.py) are rp_rcp 1 ulp, rp_rsqrt 2 ulp, rp_sincos / rp_atan 1 ulp and explicit fma elsewhere: at most four times the
+oracle's per-operation error; another factor of two covers the other association of sums and the closed-form solve against pivoted
+elimination.  A defect moves every element, luck does not: the RMS criterion gets half the factor.  Costs:
+max |c_D - c_X| / c_X <= 8 max |c_O - c_X| / c_X + _bitid.summation_bound(N).
+
+A candidate whose ORACLE rows are further than 1e-10 from the reference took another branch than the reference or is ill-conditioned
+(s' > 0.001, the EPS clamps, the segment index, the orientation wrap, the >= 0 clamps of the extension; a cosine or 1 - k_r d that is a
+rounding residue); it is left out of E and R -- decided from O and X only, never from D.  tests/test_xref_abi.py caps how many.
+
+usage (GPU box): python tests/_xref.py [out_file]      writes the table of profiles/accuracy_xref.txt"""
+import dataclasses
+import functools
+import math
+import os
+import sys
+
+import numpy as np
+
+if __name__ == "__main__":   # (as a script: the paths tests/conftest.py sets up for the suite)
+    _repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [_repo, os.path.join(_repo, "commonroad-reactive-planner_amd"), os.path.join(_repo, "tests")]
+
+import _dd as dd
+from _bitid import summation_bound
+from _dd import DD
+
+from commonroad_rp_amd import workloads as W
+from commonroad_rp_amd._capi import (PlanInputs, make_params, make_cost, copy_params, ARRAY_NAMES, FLAG_DRAW_ALL, FLAG_MATERIALIZE_ALL,
+                                     FLAG_SKIP_COLLISION, COST_DEFAULT, COST_FAILSAFE, LON_STOPPING, LON_VELOCITY_KEEPING)
+from commonroad_rp_amd.collision import ObstacleTables
+from commonroad_rp_amd.coordinate_system import CoordinateSystem
+
+LD = np.longdouble
+HAVE_LONGDOUBLE = np.finfo(LD).nmant >= 63
+SKIP_REASON = (f"np.longdouble has a {np.finfo(LD).nmant}-bit significand here; the extended-precision reference needs at least 63 bits "
+               "(x87 80-bit, as on x86-64 hosts)")
+
+X, Y, THETA, V, A, KAPPA, KAPPA_DOT, S, D, THETA_CL, S_DOT, S_DDOT, D_DOT, D_DDOT = range(14)
+ROWS = tuple(ARRAY_NAMES)
+EPS = LD(1e-5)              # reactive_planner.py _EPS: the double
+S_VEL_MIN = LD(0.001)       # the double
+PI = LD(math.pi)            # make_valid_orientation's doubles
+TWO_PI = LD(2.0 * math.pi)
+
+MARGIN_MAX, MARGIN_RMS, FLOOR_MAX, FLOOR_RMS = 8.0, 4.0, 8.0, 2.0
+LEFT_OUT_ABOVE = 1e-10      # oracle further than this from the reference: another branch or ill-conditioned
+ORACLE_BOUND = 1e-11        # what tests/test_xref_abi.py holds E_O to (measured: 3.2e-12 at most)
+MAX_EVALUATED = 64
+DT = 0.1
+
+
+# ---- the cases -------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Spec:
+    name: str
+    n_steps: int          # N + 1
+    path: str             # straight_nw | straight_se | arc | scurve
+    start: str            # keep | fast | stop | low | still0 | still002
+    cost: str = "default"  # default | failsafe
+    w_a: float = 5.0
+    desired_d: float = 0.0
+    draw: bool = False
+    ragged_T: bool = False   # time samples that are no clean multiples of dt
+    degenerate: bool = False  # a standstill start: s' crosses 0.001 inside the row -- up to 2 % of the candidates may be left out
+
+
+CASES = (
+    Spec("straight_keep_n16", 16, "straight_nw", "keep"),
+    Spec("arc_keep_n17", 17, "arc", "keep", w_a=1.0, desired_d=0.5),
+    Spec("scurve_stop_n64", 64, "scurve", "stop"),
+    Spec("arc_low_n65", 65, "arc", "low", w_a=1.0),
+    Spec("straight_fast_n111", 111, "straight_se", "fast", desired_d=0.5),
+    Spec("scurve_keep_n111", 111, "scurve", "keep", w_a=1.0, ragged_T=True),
+    Spec("arc_failsafe_n64", 64, "arc", "keep", cost="failsafe", ragged_T=True),
+    Spec("straight_stop_n65", 65, "straight_se", "stop", w_a=1.0, desired_d=0.5),
+    Spec("scurve_low_failsafe_n17", 17, "scurve", "low", cost="failsafe"),
+    Spec("straight_still0_n65", 65, "straight_nw", "still0", degenerate=True),
+    Spec("scurve_still002_n111", 111, "scurve", "still002", w_a=1.0, degenerate=True),
+    Spec("arc_draw_n17", 17, "arc", "keep", draw=True, desired_d=0.5),
+    Spec("scurve_draw_low_n65", 65, "scurve", "low", draw=True, w_a=1.0),
+    Spec("arc_draw_stop_n16", 16, "arc", "stop", draw=True),
+)
+CASE_NAMES = tuple(c.name for c in CASES)
+_BY_NAME = {c.name: c for c in CASES}
+
+
+def _path(kind):
+    if kind == "scurve":   # tests/_fuzz.random_path's sum of three sines, a fixed draw of it
+        from _fuzz import random_path
+        for seed in range(1000, 1100):
+            rng = np.random.default_rng(seed)
+            n, k = int(rng.integers(60, 420)), int(rng.integers(0, 4))
+            if n >= 330 and k >= 2:
+                return random_path(np.random.default_rng(seed))
+        raise AssertionError("no S-curve among the seeds")
+    s = np.arange(0.0, 450.0 if kind.startswith("straight") else 150.0, 1.0)
+    if kind == "straight_nw":     # x, y near -500 / +500: an ulp of the coordinate is 1.1e-13
+        x0, y0, th = -511.0, 509.0, np.full(len(s), -0.3)
+    elif kind == "straight_se":
+        x0, y0, th = 512.5, -508.25, np.full(len(s), 2.5)
+    else:                         # constant curvature, radius 25 m
+        x0, y0, th = 40.0, -70.0, 0.4 + s / 25.0
+    return np.stack((x0 + np.cumsum(np.cos(th)), y0 + np.cumsum(np.sin(th))), axis=1)
+
+
+@dataclasses.dataclass
+class Case:
+    spec: Spec
+    inp: PlanInputs
+    co: object
+    tables: object      # oracle.OracleTables
+
+
+@functools.lru_cache(maxsize=None)
+def case(name) -> Case:
+    from oracle import oracle
+    sp = _BY_NAME[name]
+    N = sp.n_steps - 1
+    horizon = N * DT
+    co = CoordinateSystem(_path(sp.path))
+    v0 = {"keep": 7.0 if sp.path == "arc" else 9.0, "fast": 30.0, "stop": 8.0 if N > 20 else 4.0, "low": 2.0, "still0": 0.0, "still002": 0.02}[sp.start]
+    low, stopping, still = sp.start == "low", sp.start == "stop", sp.start.startswith("still")
+    s0 = 12.3
+    x0_lon = [s0, v0, 0.0 if still else 0.15]
+    d0 = 2.0 if sp.path == "arc" else 0.3   # (on the arc |d| goes up to 4 m: 1 - k_r d and the kappa and a formulas do real work)
+    calm = still or stopping   # (d' = d_dot / s_dot: next to s_dot = 0 only small lateral moves are drivable in high-velocity mode)
+    x0_lat = [d0, 0.0 if calm else (0.02 if low else 0.05), 0.0 if calm else -0.02]
+    theta0 = float(np.interp(s0, co.ref_pos, np.unwrap(co.ref_theta)) + (math.atan(x0_lat[1]) if low else math.asin(x0_lat[1] / max(v0, 0.5))))
+    ks = sorted({2, max(3, N // 3), max(4, (2 * N) // 3 + 1), N})   # shortest time sample 2 dt: almost the whole row is extension
+    T = np.array([DT * k for k in ks])
+    if sp.ragged_T:
+        # the grid points as np.arange makes them (tests/_fuzz.py:55-56), and the inner samples 0.03 s off the grid: their polynomials
+        # are evaluated one step beyond T
+        T = np.array([float(np.arange(0, round(t + DT, 2), DT)[-1]) for t in T])
+        T[1:-1] += 0.03
+    nL, nD = 7, 9
+    if stopping:
+        L = s0 + v0 * np.linspace(0.3 * T[1], 0.75 * T[-1], nL)   # (targets the longer time samples can come to rest at)
+    else:
+        lo, hi = W.velocity_range(v0, horizon)
+        L = np.linspace(lo, min(hi, v0 + 3.0), nL)
+    # (lateral moves a horizon of this length can make)
+    width = 0.05 if calm else min(3.5, max(0.5, 0.35 * horizon))
+    D = W._with_d0(np.clip(d0 + np.linspace(-width, width, nD - 1), -4.0, 4.0), x0_lat[0])
+    flags = FLAG_SKIP_COLLISION | (FLAG_DRAW_ALL if sp.draw else 0)
+    params = make_params(dt=DT, N=N, low_vel_mode=low, lon_mode=LON_STOPPING if stopping else LON_VELOCITY_KEEPING, constraint_mask=31,
+                         flags=flags, x0_lon=x0_lon, x0_lat=x0_lat, x0_orientation=theta0, **W.VEHICLE2)
+    if sp.cost == "failsafe":
+        cost = make_cost(COST_FAILSAFE)
+    else:
+        cost = make_cost(COST_DEFAULT, w_a=sp.w_a, desired_speed=None if stopping else v0 + 1.0, desired_d=sp.desired_d,
+                         desired_s=s0 + 20.0 if stopping else None)
+    inp = PlanInputs(params, cost, T, W.traj_len_of(T, DT), L, D)
+    return Case(sp, inp, co, oracle.OracleTables.from_coordinate_system(co, ObstacleTables()))
+
+
+def with_flags(inp, set_=0, clear=0):
+    p = copy_params(inp.params)
+    p.flags = (p.flags & ~clear) | set_
+    return PlanInputs(p, inp.cost, inp.T, inp.traj_len, inp.L, inp.D)
+
+
+def production(inp):
+    """costs only: no draw mode, no rows"""
+    return with_flags(inp, clear=FLAG_DRAW_ALL | FLAG_MATERIALIZE_ALL)
+
+
+def _readonly(*arrays):
+    for a in arrays:
+        if a is not None:
+            a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_run(name):
+    """(status, cost, coeffs [C, 13], states [C, 14, n]) of the double oracle, read-only"""
+    from oracle import oracle
+    c = case(name)
+    run = oracle.plan(c.inp, c.tables, want_states=True)
+    return _readonly(run.status, run.cost, run.coeffs, run.states)
+
+
+@functools.lru_cache(maxsize=None)
+def subset(name):
+    """Up to MAX_EVALUATED candidates that have rows (feasible or colliding; in draw mode also the infeasible ones): the first and the last,
+    the shortest and the longest time sample, the current lateral offset d0 on a sample, the rest evenly spread."""
+    c = case(name)
+    status = oracle_run(name)[0]
+    lab = status & 3
+    have = (lab == 1) | (lab == 3) | (c.spec.draw & (lab == 2) & ((status >> 8) > 0))
+    idx = np.flatnonzero(have)
+    assert len(idx) >= 8, (name, len(idx))
+    nLD = len(c.inp.L) * len(c.inp.D)
+    iT, iD = idx // nLD, idx % len(c.inp.D)
+    pick = {int(idx[0]), int(idx[-1])}
+    pick.add(int(idx[np.argmin(c.inp.T[iT])]))
+    pick.add(int(idx[np.argmax(c.inp.T[iT])]))
+    d0 = idx[c.inp.D[iD] == c.inp.params.x0_lat[0]]
+    pick |= {int(d0[0]), int(d0[-1])} if len(d0) else set()
+    room = MAX_EVALUATED - len(pick)
+    pick |= set(int(i) for i in idx[np.unique(np.linspace(0, len(idx) - 1, min(room, len(idx))).astype(int))][:room])
+    out = np.array(sorted(pick)[:MAX_EVALUATED], dtype=np.int64)
+    return _readonly(out)[0]
+
+
+# ---- the reference ---------------------------------------------------------------------------------------------------------------
+# Working precision: double-word longdouble arithmetic (tests/_dd.py, about 128 bits), so that what is handed out -- rows, costs and
+# coefficients ROUNDED to longdouble -- is the correctly rounded truth also on rows that are differences of nearly equal numbers.
+def _dd_in(a):
+    """doubles (or longdoubles) as double-word numbers, exactly"""
+    return a if isinstance(a, DD) else DD(np.asarray(a).astype(LD))
+
+
+def _solve(a, b):
+    """a x = b by elimination with partial pivoting (np.linalg.solve has no such type); a: small integers, b: double-word arrays"""
+    n = len(b)
+    a = [[DD(LD(v)) for v in row] for row in a]
+    b = list(b)
+    for k in range(n):
+        p = max(range(k, n), key=lambda r: abs(float(a[r][k].hi)))
+        a[k], a[p], b[k], b[p] = a[p], a[k], b[p], b[k]
+        for r in range(k + 1, n):
+            f = a[r][k] / a[k][k]
+            for q in range(k, n):
+                a[r][q] = a[r][q] - f * a[k][q]
+            b[r] = b[r] - f * b[k]
+    x = [None] * n
+    for k in reversed(range(n)):
+        acc = b[k]
+        for q in range(k + 1, n):
+            acc = acc - a[k][q] * x[q]
+        x[k] = acc / a[k][k]
+    return x
+
+
+def _quintic(x0, xd, T):
+    """polynomial_trajectory.py:292-320.  The system is solved for h_k T^k (k = 3, 4, 5): the same solution exactly, from a matrix of
+    small integers, so that the elimination loses no digits to the spread of T^3 .. T^5."""
+    t2 = T * T
+    t3, t4 = t2 * T, t2 * t2
+    t5 = t4 * T
+    g = _solve([[1, 1, 1], [3, 4, 5], [6, 12, 20]],
+               [xd[0] - (x0[0] + x0[1] * T + x0[2].scaled(0.5) * t2), (xd[1] - (x0[1] + x0[2] * T)) * T, (xd[2] - x0[2]) * t2])
+    return [x0[0], x0[1], x0[2].scaled(0.5), g[0] / t3, g[1] / t4, g[2] / t5]
+
+
+def _quartic(x0, vd, T):
+    """polynomial_trajectory.py:341-360 (solved for h_k T^k, as above)"""
+    t2 = T * T
+    t3 = t2 * T
+    g = _solve([[3, 4], [6, 12]], [(vd - x0[1] - x0[2] * T) * T, -(x0[2] * t2)])
+    return [x0[0], x0[1], x0[2].scaled(0.5), g[0] / t3, g[1] / (t2 * t2), x0[0] * 0]
+
+
+def _pos(c, t, t2, t3, t4, t5):
+    return c[0] + c[1] * t + c[2] * t2 + c[3] * t3 + c[4] * t4 + c[5] * t5
+
+
+def _vel(c, t, t2, t3, t4):
+    return c[1] + 2 * c[2] * t + 3 * c[3] * t2 + 4 * c[4] * t3 + 5 * c[5] * t4
+
+
+def _acc(c, t, t2, t3):
+    return 2 * c[2] + 6 * c[3] * t + 12 * c[4] * t2 + 20 * c[5] * t3
+
+
+def sample(inp, idx):
+    """sampling.py:202-242 for the candidates `idx` -> (lon, lat: six double-word arrays [m] each, traj_len [m], T [m])"""
+    p = inp.params
+    idx = np.asarray(idx, dtype=np.int64)
+    nL, nD = len(inp.L), len(inp.D)
+    iT, rem = np.divmod(idx, nL * nD)
+    iL, iD = np.divmod(rem, nD)
+    m = len(idx)
+    T = _dd_in(inp.T[iT])
+    const = lambda v: _dd_in(np.full(m, float(v)))
+    x0_lon, x0_lat = [const(v) for v in p.x0_lon], [const(v) for v in p.x0_lat]
+    zero = const(0.0)
+    if p.lon_mode == LON_STOPPING:
+        lon = _quintic(x0_lon, (_dd_in(inp.L[iL]), zero, zero), T)
+    else:
+        lon = _quartic(x0_lon, _dd_in(inp.L[iL]), T)
+    tau = T
+    if p.low_vel_mode:
+        t2 = T * T
+        t3, t4 = t2 * T, t2 * t2
+        s_goal = _pos(lon, T, t2, t3, t4, t3 * t2) - x0_lon[0]
+        tau = dd.where(s_goal > 0, s_goal, T)
+    lat = _quintic(x0_lat, (_dd_in(inp.D[iD]), zero, zero), tau)
+    return lon, lat, inp.traj_len[iT].astype(np.int64), np.array(inp.T[iT], dtype=np.float64)
+
+
+def _coeff_array(c):
+    """six double-word arrays [m] -> [m, 6] longdouble (rounded)"""
+    return np.stack([DD.of(k).ld() for k in c], axis=1)
+
+
+def _tangents(tb):
+    """oracle/frontend.compute_vertex_tangents, from the double vertices -> (tx, ty)"""
+    px, py = _dd_in(tb.ref_x), _dd_in(tb.ref_y)
+    ex, ey = px[1:] - px[:-1], py[1:] - py[:-1]
+    ln = dd.sqrt(ex * ex + ey * ey)
+    ux, uy = ex / ln, ey / ln
+    sx, sy = ux[:-1] + ux[1:], uy[:-1] + uy[1:]
+    ls = dd.sqrt(sx * sx + sy * sy)
+    cat = lambda first, mid, last: DD(np.concatenate((first.hi[None], mid.hi, last.hi[None])), np.concatenate((first.lo[None], mid.lo, last.lo[None])))
+    return cat(ux[0], sx / ls, ux[-1]), cat(uy[0], sy / ls, uy[-1])
+
+
+def _valid_orientation(a):
+    a = dd.mod(a, DD(TWO_PI))
+    return dd.where((a >= DD(PI)) & (a <= DD(TWO_PI)), a - DD(TWO_PI), a)
+
+
+@dataclasses.dataclass
+class Ref:
+    index: np.ndarray      # candidate indices (None: explicit polynomials)
+    lon: np.ndarray        # [m, 6] longdouble
+    lat: np.ndarray
+    traj_len: np.ndarray   # [m]
+    T: np.ndarray          # [m] double
+    states: np.ndarray     # [m, 14, n] longdouble
+    cost: np.ndarray       # [m] longdouble (of every candidate, whatever its label)
+    inter: dict            # s, d, dp, dpp, k_r, k_r_d, theta_cl per step: where a finding sits
+
+
+def evaluate(c: Case, lon, lat, traj_len):
+    """reactive_planner.py:731-960 for the polynomials lon, lat ([m, 6] arrays, or six double-word arrays each) without the feasibility
+    decisions: every candidate is evaluated over its traj_len steps and extended (the caller masks what the reference would not have).
+    -> (rows [m, 14, n], costs [m], both rounded to longdouble, intermediates)"""
+    with np.errstate(all="ignore"):   # (rows of candidates the reference drops may divide by zero: masked by the caller)
+        return _evaluate(c, lon, lat, traj_len)
+
+
+def _evaluate(c, lon, lat, traj_len):
+    p, tb, cst = c.inp.params, c.tables, c.inp.cost
+    n, m = p.N + 1, len(traj_len)
+    dt = DD(LD(p.dt))
+    low = bool(p.low_vel_mode)
+    tl = np.minimum(np.asarray(traj_len), n).astype(np.int64)
+    valid = np.arange(n)[None, :] < tl[:, None]
+    t = DD(np.arange(n).astype(LD))[None, :] * dt
+    t2 = t * t
+    t3 = t2 * t
+    t4 = t2 * t2
+    t5 = t4 * t
+    co = lambda cf: [_dd_in(cf[k])[:, None] for k in range(6)] if isinstance(cf, (list, tuple)) else [_dd_in(cf[:, k:k + 1]) for k in range(6)]
+    z = lambda a: dd.where(valid, a, 0)
+    cl, ct = co(lon), co(lat)
+    s, s_vel, s_acc = z(_pos(cl, t, t2, t3, t4, t5)), z(_vel(cl, t, t2, t3, t4)), z(_acc(cl, t, t2, t3))
+    if not low:
+        d, d_vel, d_acc = z(_pos(ct, t, t2, t3, t4, t5)), z(_vel(ct, t, t2, t3, t4)), z(_acc(ct, t, t2, t3))
+    else:
+        s1 = s - s[:, :1]
+        s2 = s1 * s1
+        s3 = s2 * s1
+        s4 = s2 * s2
+        s5 = s4 * s1
+        d, d_vel, d_acc = z(_pos(ct, s1, s2, s3, s4, s5)), z(_vel(ct, s1, s2, s3, s4)), z(_acc(ct, s1, s2, s3))
+    s_vel = dd.where(abs(s_vel) < DD(EPS), 0, s_vel)
+    d_vel = dd.where(abs(d_vel) < DD(EPS), 0, d_vel)
+    moving = s_vel > DD(S_VEL_MIN)
+    if not low:
+        safe = dd.where(moving, s_vel, 1)
+        dp = dd.where(moving, d_vel / safe, 0)
+        dpp = dd.where(moving, (d_acc - dp * s_acc) / (safe * safe), 0)
+    else:
+        dp, dpp = d_vel, d_acc
+    rp, rth, rk, rkd = (_dd_in(a) for a in (tb.ref_pos, tb.ref_theta, tb.ref_curv, tb.ref_curv_d))
+    nr = len(tb.ref_pos)
+    # np.argmax(ref_pos > s) - 1 (outside [ref_pos[0], ref_pos[-1]) the reference's index wraps: such steps are out of domain and masked)
+    k = np.clip(np.searchsorted(rp.hi, s.hi, side="right") - 1, 0, nr - 2)
+    k = np.clip(np.where(s < rp[k], k - 1, k), 0, nr - 2)   # (s.hi on a vertex, s below it)
+    seg = rp[k + 1] - rp[k]
+    lam = (s - rp[k]) / seg
+    th_ref = _valid_orientation((rth[k + 1] - rth[k]) * (s - rp[k]) / seg + rth[k])
+    theta_cl = dd.atan(dp)        # np.arctan2(dp, 1.0)
+    theta = theta_cl + th_ref
+    use = moving | low
+    if not use[valid].all():   # the standstill branch carries theta from the step before
+        theta = theta.copy()
+        for i in range(n):
+            prev = dd.broadcast_to(DD(LD(p.x0_orientation)), (m,)) if i == 0 else theta[:, i - 1]
+            theta[:, i] = dd.where(use[:, i], theta[:, i], prev)
+        theta_cl = dd.where(use, theta_cl, theta - th_ref)
+    k_r = (rk[k + 1] - rk[k]) * lam + rk[k]
+    k_r_d = (rkd[k + 1] - rkd[k]) * lam + rkd[k]
+    one_krd = 1 - k_r * d
+    sin_t, cos_t = dd.sincos(theta_cl)
+    tan_t = sin_t / cos_t
+    kappa = (dpp + (k_r * dp + k_r_d * d) * tan_t) * cos_t * (cos_t / one_krd) ** 2 + (cos_t / one_krd) * k_r
+    v = s_vel * (one_krd / cos_t)
+    a = s_acc * one_krd / cos_t + ((s_vel * s_vel) / cos_t) * (one_krd * tan_t * (kappa * one_krd / cos_t - k_r) - (k_r_d * d + k_r * dp))
+    # (s, d) -> (x, y): the scalar formulas of oracle/rp_oracle.c
+    tx, ty = _tangents(tb)
+    rx, ry = _dd_in(tb.ref_x), _dd_in(tb.ref_y)
+    px, py = rx[k] + lam * (rx[k + 1] - rx[k]), ry[k] + lam * (ry[k + 1] - ry[k])
+    ax, ay = tx[k] + lam * (tx[k + 1] - tx[k]), ty[k] + lam * (ty[k + 1] - ty[k])
+    tn = dd.sqrt(ax * ax + ay * ay)
+    x, y = px - d * (ay / tn), py + d * (ax / tn)
+    st = {X: z(x), Y: z(y), THETA: z(theta), V: z(v), A: z(a), KAPPA: z(kappa), S: z(s), D: z(d), THETA_CL: z(theta_cl), S_DOT: z(s_vel),
+          S_DDOT: z(s_acc), D_DOT: z(d_vel), D_DDOT: z(d_acc)}
+    kd = dd.zeros((m, n))
+    kd[:, 1:] = st[KAPPA][:, 1:] - st[KAPPA][:, :-1]   # np.diff over the padded array
+    st[KAPPA_DOT] = kd
+    _enlarge(st, tl, n, dt)
+    inter = {key: val.ld() for key, val in dict(s=s, d=d, dp=dp, dpp=dpp, k_r=k_r, k_r_d=k_r_d, theta_cl=theta_cl, one_krd=one_krd, cos=cos_t).items()}
+    return np.stack([st[r].ld() for r in range(14)], axis=1), _cost(cst, st, n).ld(), inter
+
+
+def _enlarge(st, tl, n, dt):
+    """trajectories.py:168-197 and :302-332 as oracle/numpy_loop._enlarge states them, for the candidates with tl < n, all at once.
+    The quirks: a[-1] is read AFTER the row is extended (= a[last]); s_ddot[-1] and d_ddot[-1] BEFORE (= the zero padding), so that
+    s_dot and d_dot keep their last value."""
+    m = len(tl)
+    rows = np.arange(m)
+    last = tl - 1
+    ext = np.arange(n)[None, :] >= tl[:, None]
+    at_last = {r: st[r][rows, last][:, None] for r in range(14)}
+    t = DD((np.arange(n)[None, :] - last[:, None]).astype(LD)) * dt        # (1 .. n - L) dt on the extended steps
+    v_temp = at_last[V] + t * at_last[A]
+    v_temp = dd.where(v_temp >= 0, v_temp, 0)
+    sin_l, cos_l = dd.sincos(at_last[THETA])
+    step_x, step_y = dd.where(ext, dt * v_temp * cos_l, 0), dd.where(ext, dt * v_temp * sin_l, 0)
+    cum_x, cum_y = dd.zeros((m, n)), dd.zeros((m, n))
+    for i in range(1, n):   # np.cumsum
+        cum_x[:, i] = cum_x[:, i - 1] + step_x[:, i]
+        cum_y[:, i] = cum_y[:, i - 1] + step_y[:, i]
+    s_dot_temp = dd.where(at_last[S_DOT] >= 0, at_last[S_DOT], 0)
+    new = {A: at_last[A], V: v_temp, THETA: at_last[THETA], KAPPA: at_last[KAPPA], KAPPA_DOT: at_last[KAPPA_DOT], X: at_last[X] + cum_x,
+           Y: at_last[Y] + cum_y, S_DOT: s_dot_temp, D_DOT: at_last[D_DOT], S_DDOT: at_last[S_DDOT], D_DDOT: at_last[D_DDOT],
+           THETA_CL: at_last[THETA_CL], S: at_last[S] + t * at_last[S_DOT], D: at_last[D] + t * at_last[D_DOT]}
+    for r in range(14):
+        st[r] = dd.where(ext, new[r], st[r])
+
+
+def _cost(c, st, n):
+    """cost_function.py:51-71 (default), :82-92 (fail-safe), plain sums in order"""
+    a, v, s, d, th = st[A], st[V], st[S], st[D], st[THETA_CL]
+    total = lambda row: dd.total(row, n, lambda i: row[:, i])
+    q = LD(0.25)
+    tail = total((q * abs(th)) ** 2) + (5 * abs(th[:, -1])) ** 2
+    if c.kind == COST_FAILSAFE:
+        return total(a * a) + total((q * d) ** 2) + (20 * d[:, -1]) ** 2 + tail
+    cost = total((LD(c.w_a) * a) ** 2)
+    if not math.isnan(c.desired_speed):
+        vd = LD(c.desired_speed)
+        cost = cost + total((5 * (v - vd)) ** 2) + (50 * (v[:, -1] - vd) ** 2) + (100 * (v[:, int(n / 2)] - vd) ** 2)
+    if not math.isnan(c.desired_s):
+        ds = LD(c.desired_s)
+        cost = cost + total((q * (ds - s)) ** 2) + (20 * (ds - s[:, -1])) ** 2
+    dsd = LD(c.desired_d)
+    cost = cost + total((q * (dsd - d)) ** 2) + (20 * (dsd - d[:, -1])) ** 2
+    return cost + tail
+
+
+@functools.lru_cache(maxsize=None)
+def reference_for(name, indices) -> Ref:
+    """the reference of the candidates `indices` (a tuple) of a case, read-only"""
+    c = case(name)
+    idx = np.array(indices, dtype=np.int64)
+    lon, lat, tl, T = sample(c.inp, idx)
+    st, cost, inter = evaluate(c, lon, lat, tl)
+    lon, lat = _coeff_array(lon), _coeff_array(lat)
+    _readonly(idx, lon, lat, tl, T, st, cost, *inter.values())
+    return Ref(idx, lon, lat, tl, T, st, cost, inter)
+
+
+def reference(name) -> Ref:
+    return reference_for(name, tuple(int(i) for i in subset(name)))
+
+
+@functools.lru_cache(maxsize=None)
+def coeffs_tier(name):
+    """The rp_plan_coeffs tier: the reference's coefficients of the case's subset, ROUNDED TO DOUBLE, evaluated exactly by the reference
+    and in double by the oracle -> (lon [m, 6], lat [m, 6], T [m], traj_len [m] doubles / int32, Ref, oracle status, cost, states)."""
+    from oracle import oracle
+    c = case(name)
+    r = reference(name)
+    lon, lat = r.lon.astype(np.float64), r.lat.astype(np.float64)
+    tl = r.traj_len.astype(np.int32)
+    st, cost, inter = evaluate(c, lon.astype(LD), lat.astype(LD), tl)
+    run = oracle.plan_coeffs(c.inp.params, c.inp.cost, c.tables, lon, lat, tl, want_states=True)
+    _readonly(lon, lat, tl, st, cost, run.status, run.cost, run.states)
+    return lon, lat, r.T, tl, Ref(None, lon.astype(LD), lat.astype(LD), r.traj_len, r.T, st, cost, inter), run.status, run.cost, run.states
+
+
+# ---- the comparison --------------------------------------------------------------------------------------------------------------
+def compared_steps(status, n, draw):
+    """[m, n] bool: the elements a result is compared on -- every step of a feasible / colliding candidate; in draw mode an infeasible
+    candidate up to the step before its first failure (tests/_fuzz.py:186-201); nothing of a candidate without rows"""
+    status = np.asarray(status).astype(np.int64)
+    lab = status & 3
+    full = (lab == 1) | (lab == 3)
+    upto = np.where(full, n, np.where((lab == 2) & bool(draw), status >> 8, 0))
+    return np.arange(n)[None, :] < upto[:, None]
+
+
+def left_out(Xs, O, mask):
+    """[m] bool: candidates whose ORACLE rows are further than LEFT_OUT_ABOVE from the reference on a compared element (or not finite)"""
+    dev = np.abs(np.asarray(O).astype(LD) - Xs)
+    bad = ~(dev <= LEFT_OUT_ABOVE)
+    return (bad & mask[:, None, :]).any(axis=(1, 2))
+
+
+@dataclasses.dataclass
+class RowResult:
+    row: str
+    scale: float
+    e_o: float
+    e_d: float
+    r_o: float
+    r_d: float
+    e_bound: float
+    r_bound: float
+
+    @property
+    def ok(self):
+        return bool(self.e_d <= self.e_bound) and bool(self.r_d <= self.r_bound)
+
+    def line(self):
+        ratio = lambda a, b: (f"{a / b:8.2f}" if b > 0 else ("    0/0 " if a == 0 else "    inf "))
+        return (f"{self.row:>9s} scale {self.scale:9.3e}  E_O {self.e_o:9.3e} E_D {self.e_d:9.3e} ({ratio(self.e_d, self.e_o)}) bound {self.e_bound:9.3e}  "
+                f"R_O {self.r_o:9.3e} R_D {self.r_d:9.3e} ({ratio(self.r_d, self.r_o)}) bound {self.r_bound:9.3e}{'' if self.ok else '   EXCEEDS'}")
+
+
+def _errors(Xs, B, sel):
+    """max and root mean square of |B - X| per row over the elements sel [m, n]"""
+    dev = np.abs(np.asarray(B).astype(LD) - Xs)
+    dev = np.where(sel[:, None, :], dev, LD(0))
+    cnt = max(int(sel.sum()), 1)
+    return dev.max(axis=(0, 2)).astype(np.float64), np.sqrt((dev * dev).sum(axis=(0, 2)) / cnt).astype(np.float64)
+
+
+def compare_rows(Xs, O, Dv, mask):
+    """The rule of this module's docstring for one case: Xs [m, 14, n] longdouble, O and Dv doubles, mask [m, n] the compared elements.
+    Returns (list of RowResult, number of candidates left out).  A non-finite device value on a compared element exceeds every bound."""
+    out = left_out(Xs, O, mask)
+    sel = mask & ~out[:, None]
+    e_o, r_o = _errors(Xs, O, sel)
+    with np.errstate(invalid="ignore"):
+        e_d, r_d = _errors(Xs, np.where(np.isfinite(Dv), Dv, np.inf), sel)
+    scale = np.where(sel[:, None, :], np.abs(Xs), LD(0)).max(axis=(0, 2)).astype(np.float64)
+    sp = np.spacing(scale)
+    return [RowResult(ROWS[r], float(scale[r]), float(e_o[r]), float(e_d[r]), float(r_o[r]), float(r_d[r]),
+                      MARGIN_MAX * float(e_o[r]) + FLOOR_MAX * float(sp[r]), MARGIN_RMS * float(r_o[r]) + FLOOR_RMS * float(sp[r]))
+            for r in range(14)], int(out.sum())
+
+
+def failures(rows):
+    return [r.line() for r in rows if not r.ok]
+
+
+def compare_costs(cX, cO, cD, sel, N):
+    """costs of the candidates sel [m] (feasible ones that are not left out) -> (relative error of the oracle, of the device, bound)"""
+    if not sel.any():
+        return 0.0, 0.0, summation_bound(N)
+    cx = cX[sel]
+    rel = lambda c: float((np.abs(np.asarray(c)[sel].astype(LD) - cx) / cx).max())
+    e_o = rel(cO)
+    with np.errstate(invalid="ignore"):
+        e_d = rel(np.where(np.isfinite(cD), cD, np.inf))
+    return e_o, e_d, MARGIN_MAX * e_o + summation_bound(N)
+
+
+def compare_coeffs(cX, cO, cD):
+    """coefficients [..., 6]: |c_D - c_X| <= 8 |c_O - c_X| + 8 spacing(|c_X|) each -> (worst oracle error, worst device error, ok)"""
+    e_o = np.abs(np.asarray(cO).astype(LD) - cX).astype(np.float64)
+    e_d = np.abs(np.asarray(cD).astype(LD) - cX).astype(np.float64)
+    bound = MARGIN_MAX * e_o + FLOOR_MAX * np.spacing(np.abs(cX.astype(np.float64)))
+    return e_o, e_d, bool((e_d <= bound).all())
+
+
+def case_views(name):
+    """what both test modules compare on: (Ref, oracle status / cost / states / coeffs of the subset, compared elements)"""
+    r = reference(name)
+    status, cost, coeffs, states = oracle_run(name)
+    c = case(name)
+    mask = compared_steps(status[r.index], c.inp.params.N + 1, c.spec.draw)
+    return r, status[r.index], cost[r.index], states[r.index], coeffs[r.index], mask
+
+
+# ---- launch variants, known exceedances, and the script form: the table of profiles/accuracy_xref.txt --------------------------------
+# The launch variants that store rows.  A name says what its options FORCE; what the library chooses beyond that (one launch or two,
+# lanes of the default) is read back, reported, and tests/test_xref.py checks that the variants together reach every kernel instance.
+STATE_VARIANTS = {
+    "default": {},                                                            # the library's own choice for a small batch that stores rows
+    "lanes16": {"lanes": 16},                                                 # 16 lanes per candidate; one launch where tables and profile rows fit in LDS
+    "two_kernel_16": {"fused_lon": 0, "lanes": 16},                           # rp_lon_kernel + rp_eval_kernel; rows of 64 steps: the lean (fixed-stride) step block
+    "two_kernel_16_generic": {"fused_lon": 0, "lanes": 16, "fixed_stride": 0},   # ... never the lean step block
+    "two_kernel_32": {"fused_lon": 0, "lanes": 32},
+    "two_kernel_64": {"fused_lon": 0, "lanes": 64},
+}
+# (lanes per candidate, single launch, fixed-stride variant) of rp_eval_kernel that the variants have to reach between them
+KERNEL_INSTANCES = {(16, 1, 0), (32, 1, 0), (64, 1, 0), (16, 0, 0), (16, 0, 1), (32, 0, 0), (64, 0, 0)}
+
+# Rows that exceed the rule on an MI355X: (tier, case, row) -> diagnosis ("Against an extended-precision reference").
+# tests/test_xref.py asserts each of them on its own, expected to fail, strictly; every other row of the same comparisons is asserted as usual.
+_SOLVE = ("rounding of c3 .. c5 in the closed-form solve (here behind the oracle's elimination) through cancelling terms, the same error at "
+          "every step of a candidate: ")
+KNOWN_EXCEEDANCES = {
+    ("single", "straight_keep_n16", "a"): _SOLVE + "s_ddot = 2 c2 + 6 c3 t + 12 c4 t^2 of the T = 2 dt and T = 1.1 s candidates, 8 and 13 ulp of the scale (oracle 0.1 and 2); RMS 13x",
+    ("single", "straight_keep_n16", "s_ddot"): _SOLVE + "as row a of this case; RMS 14x",
+    ("single", "straight_fast_n111", "s_ddot"): _SOLVE + "T = 2 dt: 8 ulp (oracle 3) carried over 108 extended steps; RMS 7x",
+    ("single", "straight_still0_n65", "d_ddot"): "d_ddot of the T = 2 dt candidate is a rounding residue (scale 2e-18) repeated over 62 extended steps: max 1.0x the oracle, RMS 7.7x",
+    ("winner", "straight_fast_n111", "kappa"): _SOLVE + "lateral quintic over T = 11 s to the offset it starts at: d_dot 33 ulp (oracle 6); one candidate, RMS 6x",
+    ("winner", "straight_fast_n111", "theta_cl"): _SOLVE + "as row kappa of this case; RMS 7x",
+    ("winner", "straight_fast_n111", "d_dot"): _SOLVE + "as row kappa of this case; RMS 7x",
+    ("winner", "straight_fast_n111", "d_ddot"): _SOLVE + "as row kappa of this case; RMS 7x",
+    ("explicit", "scurve_keep_n111", "a"): "EVALUATION, one element of a batch of 61: candidate 48 (T = 2 dt, 3.5 m sideways), step 1: d_ddot = -0.37 from Horner terms of 2600, "
+                                           "the device 6e-14 off (0.14 ulp of the terms), the oracle 3e-15; a inherits 0.46 of it: 14x the oracle's largest error of the row (RMS 1.7x)",
+}
+
+
+def launch_of(ctx):
+    """(kernel, lanes per candidate, single launch, fixed-stride variant) of the last plan"""
+    return ctx.last_kernel(), ctx.get_option("last_lanes"), ctx.get_option("last_single_launch"), ctx.get_option("last_fixed_stride")
+
+
+def forced_launch_differences(opts, got):
+    """what a launch (launch_of) has that the options forbid"""
+    kernel, lanes, single, fixed = got
+    found = [] if kernel == "rp_eval_kernel" else [f"kernel {kernel}"]
+    if opts.get("lanes") and lanes != opts["lanes"]:
+        found.append(f"{lanes} lanes, not {opts['lanes']}")
+    if opts.get("fused_lon", 1) == 0 and single:
+        found.append("one launch, not two kernels")
+    if opts.get("fixed_stride", 1) == 0 and fixed:
+        found.append("the fixed-stride variant")
+    return found
+
+
+def device_rows(ctx, name, variant):
+    """FLAG_MATERIALIZE_ALL plan of a case on a launch variant that stores rows -> (states of the subset, launch_of); what the variant's
+    options force is what ran"""
+    opts = STATE_VARIANTS[variant]
+    c = case(name)
+    saved = {k: ctx.get_option(k) for k in opts}
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    try:
+        ctx.set_coordinate_system(c.co)
+        ctx.set_obstacles(ObstacleTables())
+        ctx.plan(with_flags(c.inp, set_=FLAG_MATERIALIZE_ALL))
+        got = launch_of(ctx)
+        found = forced_launch_differences(opts, got)
+        assert not found, f"{name} on {variant}: ran {got}: " + "; ".join(found)
+        states = ctx.fetch_states()
+    finally:
+        for k, v in saved.items():
+            ctx.set_option(k, v)
+    return states[subset(name)], got
+
+
+@functools.lru_cache(maxsize=None)
+def production_feasible(name):
+    """[m] bool: the candidates of the subset that a production-mode plan costs (draw mode keeps candidates the pre-filter drops)"""
+    from oracle import oracle
+    c = case(name)
+    status = oracle_run(name)[0] if not c.spec.draw else oracle.plan(production(c.inp), c.tables, want_states=False).status
+    return _readonly((status[subset(name)] & 3) == 1)[0]
+
+
+def single_candidates(name):
+    """positions in the subset of the three candidates rp_eval_one is held to: the first, the middle and the last that a production-mode
+    plan costs and the comparison does not leave out"""
+    r, status, cost, states, coeffs, mask = case_views(name)
+    feas = np.flatnonzero(((status & 3) == 1) & production_feasible(name) & ~left_out(r.states, states, mask))
+    return np.array([feas[0], feas[len(feas) // 2], feas[-1]])
+
+
+def main(argv):
+    from _paths import LAUNCH_PATHS
+    from commonroad_rp_amd._capi import RpContext
+    if not HAVE_LONGDOUBLE:
+        print(SKIP_REASON)
+        return 1
+    path = argv[1] if len(argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "accuracy_xref.txt")
+    lines = ["Device and double oracle against the extended-precision reference (tests/_xref.py): per case, launch variant and row the",
+             "largest and the root-mean-square distance to the reference of the oracle (E_O, R_O) and of the device (E_D, R_D), the ratio",
+             "device / oracle in brackets, and the bound the device is held to (tests/test_xref.py).  A variant whose figures are those of",
+             "an earlier one is named only.  EXCEEDS (known): a row tests/test_xref.py expects to fail, diagnosis in DESIGN.md section 2.", ""]
+    bad = known = 0
+
+    def block(tier, name, rows):
+        nonlocal bad, known
+        out = []
+        for x in rows:
+            is_known = not x.ok and (tier, name, x.row) in KNOWN_EXCEEDANCES
+            out.append("  " + x.line() + (" (known)" if is_known else ""))
+            bad += (not x.ok) and not is_known
+            known += is_known
+        return out
+
+    ctx = RpContext(0)
+    for name in CASE_NAMES:
+        r, ost, ocost, ostates, ocoeffs, mask = case_views(name)
+        c = case(name)
+        seen = {}
+        for variant in STATE_VARIANTS:
+            got_rows, got = device_rows(ctx, name, variant)
+            rows, n_out = compare_rows(r.states, ostates, got_rows, mask)
+            text = block("rows", name, rows)
+            head = f"{name}  {variant}  ran {got[1]} lanes, {'one launch' if got[2] else 'two kernels'}{', fixed stride' if got[3] else ''}"
+            if tuple(text) in seen:
+                lines.append(head + f": the figures of {seen[tuple(text)]}")
+            else:
+                lines.append(head + f"  ({len(r.index)} candidates, {n_out} left out, {int(mask.sum())} elements per row)")
+                lines += text
+            seen.setdefault(tuple(text), variant)
+        sel = ((ost & 3) == 1) & production_feasible(name) & ~left_out(r.states, ostates, mask)
+        for lp, opts in LAUNCH_PATHS.items():
+            saved = {k: ctx.get_option(k) for k in opts}
+            for k, v in opts.items():
+                ctx.set_option(k, v)
+            ctx.plan(production(c.inp))
+            kernel = ctx.last_kernel()
+            cD = ctx.fetch_status()[1][r.index]
+            for k, v in saved.items():
+                ctx.set_option(k, v)
+            e_o, e_d, bound = compare_costs(r.cost, ocost, cD, sel, c.inp.params.N)
+            lines.append(f"{name}  cost on {lp} ({kernel}): oracle {e_o:9.3e} device {e_d:9.3e} bound {bound:9.3e} relative{'' if e_d <= bound else '   EXCEEDS'}")
+            bad += not e_d <= bound
+        # the explicit-polynomial tier (same coefficients on both sides), the three single candidates pooled, the winner's coefficients
+        lon, lat, T, tl, xr, xst, xcost, xstates = coeffs_tier(name)
+        p = with_flags(c.inp, set_=FLAG_MATERIALIZE_ALL).params
+        ctx.plan_coeffs(p, c.inp.cost, lon, lat, T, tl)
+        rows, n_out = compare_rows(xr.states, xstates, ctx.fetch_states(), compared_steps(xst, p.N + 1, c.spec.draw))
+        lines.append(f"{name}  explicit polynomials (rp_plan_coeffs, {n_out} left out)")
+        lines += block("explicit", name, rows)
+        out = ctx.plan(production(c.inp))
+        w = int(out.best_index)
+        js = single_candidates(name)
+        ones = np.stack([ctx.eval_one(int(r.index[j]))[0] for j in js])
+        rows, _ = compare_rows(r.states[js], ostates[js], ones, np.ones((3, c.inp.params.N + 1), dtype=bool))
+        lines.append(f"{name}  rp_eval_one of the candidates {[int(r.index[j]) for j in js]}, pooled")
+        lines += block("single", name, rows)
+        rw, oc = reference_for(name, (w,)), oracle_run(name)[2]
+        for which, cX, cO, cD in (("lon", rw.lon[0], oc[w, :6], out.best_lon_coeffs), ("lat", rw.lat[0], oc[w, 6:12], out.best_lat_coeffs)):
+            e_o, e_d, ok = compare_coeffs(cX, cO, cD)
+            ulp = np.spacing(np.abs(cX.astype(np.float64)))
+            lines.append(f"{name}  {which} coefficients c3 c4 c5 of the winner {w}, in ulp: oracle {np.round(e_o[3:] / ulp[3:], 2)} device {np.round(e_d[3:] / ulp[3:], 2)}"
+                         f"{'' if ok else '   EXCEEDS'}")
+            bad += not ok
+        lines.append("")
+    ctx.close()
+    lines.append(f"{bad} bounds exceeded, {known} known exceedances")
+    text = "\n".join(lines) + "\n"
+    with open(path, "w") as f:
+        f.write(text)
+    print(text)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))

@@ -2,7 +2,8 @@
 golden vectors of the reference, on the same inputs.  Needs a real MI355X: ``pytest -m gpu``.
 
 Tolerances (BASELINE.json north_star: 1e-6 on trajectory states, same optimal index):
-  states      |gpu - oracle| <= 1e-6 absolute (observed ~1e-12; the bound is the contract)
+  states      |gpu - oracle| <= 1e-6 absolute (the bound is the contract; what the device and the oracle are measured to be away from an
+              extended-precision reference, and a bound five orders tighter, are in tests/test_xref.py and tests/test_xref_abi.py)
   costs       1e-9 relative
   labels, first-failure reasons, counters, winner index: exact
 """
