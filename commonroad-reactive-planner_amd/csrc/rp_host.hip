@@ -68,6 +68,7 @@ struct Options {
     int shard_policy = 1;        // what decides the producer of a range's cost bits (lanes per candidate, single launch or two kernels): 1 the grid, 0 the range
     int stage_out = 1, row_padding = 1, row_align = 0, tail_split = 1;   // layout of the state rows in device memory
     int fixed_stride = 1;        // fixed-stride variant of the 16-lane kernel that stores state rows (rows of 64 doubles, no split tail): 1 = by layout, 0 never
+    int eval_waves = 0;          // ... its instance by wavefronts per SIMD: 0 = the policy (eval_waves_for), 3 | 4 pin it
     int table_window = 1;        // single-launch variant stages only the part of the reference tables a plan can touch
     int lean_broad = 1;          // rp_lon_kernel's LEAN instance (lean loop over the dynamic obstacles): 1 = whenever the table allows it, 0 never
     int fold_static = -1;        // a few static rectangles checked as rows of the dynamic table (fold_view): -1 = by rule, 0 never, 1 whenever the tables allow it
@@ -100,6 +101,7 @@ const OptionDesc kOptionTable[] = {
     {"row_align", &Options::row_align, "RP_AMD_ROW_ALIGN", false, 0, 16},
     {"tail_split", &Options::tail_split, "RP_AMD_NO_TAIL_SPLIT", true, 0, 1},
     {"fixed_stride", &Options::fixed_stride, "RP_AMD_NO_FIXED_STRIDE", true, 0, 1},
+    {"eval_waves", &Options::eval_waves, "RP_AMD_EVAL_WAVES", false, 0, 4},
     {"table_window", &Options::table_window, "RP_AMD_NO_TABLE_WINDOW", true, 0, 1},
     {"lean_broad", &Options::lean_broad, "RP_AMD_NO_LEAN_BROAD", true, 0, 1},
     {"fold_static", &Options::fold_static, "RP_AMD_FOLD_STATIC", false, -1, 1},
@@ -122,13 +124,18 @@ const OptionDesc *find_option(const char *key) {
         if (std::strcmp(d.key, key) == 0) return &d;
     return nullptr;
 }
+// a value the option takes: inside its range, and for "eval_waves" one of 0 | 3 | 4
+bool option_value_ok(const OptionDesc &d, int64_t v) {
+    if (v < d.lo || v > d.hi) return false;
+    return d.field != &Options::eval_waves || v == 0 || v >= 3;
+}
 // the environment's defaults (rp_create only)
 void options_from_environment(Options &o) {
     for (const OptionDesc &d : kOptionTable) {
         const char *e = d.env ? std::getenv(d.env) : nullptr;
         if (!e) continue;
         const int v = d.env_negates ? 0 : std::atoi(e);
-        if (v >= d.lo && v <= d.hi) o.*(d.field) = v;
+        if (option_value_ok(d, v)) o.*(d.field) = v;
     }
 }
 
@@ -204,6 +211,7 @@ struct rp_ctx {
 #ifdef RP_TIMELINE_LON
     int last_lon_grid = 0;                 // diagnostic build: workgroups of the last rp_lon_kernel launch (their timeline is printed)
 #endif
+    int last_eval_waves = 0;               // ... and the wavefronts per SIMD its rp_eval_kernel instance was compiled for: 4 the four-wave instance of the fixed-stride variant, 3 every other (read-only option "last_eval_waves"; 0: no such launch)
     int last_lon_lean = 0;                 // ... and whether its profile launch was rp_lon_kernel's LEAN instance (read-only option "last_lon_lean"; 0 also: no such launch)
     int last_collision_level = 0;          // ... and the collision level of its kernels (collision_level; read-only option "last_collision_level")
     int last_lazy = 0;                     // 0: the last plan ran eager, 1: lazy, 2: lazy attempt + eager fallback (diagnostic, rp_last_path)
@@ -412,10 +420,23 @@ inline bool fixed_stride_applies(const rp_ctx *c, const KArgs &ka) {
     return ka.row_stride == RP_ROW64 && ka.tail_split == 0 && ka.N + 1 > 16 && ka.N + 1 <= RP_ROW64 && c->opt.fixed_stride != 0;
 }
 
+// The fixed-stride variant has an instance compiled for FOUR wavefronts per SIMD (rp_kernels.h: W4 -- at most 128 vector registers, no
+// scratch; the same status words, cost bits and state rows).  Option "eval_waves" = 3 | 4 pins the instance; 0 is the policy: every
+// launch that takes the fixed-stride variant takes the four-wave instance.  Measured against the three-wave instance in alternating
+// runs (profiles/eval_four_waves_ab.txt): the headline step (cfg3 draw, 3 906 workgroups) 0.1327 -> 0.1265 ms, its evaluation kernel
+// 93.5 -> 88.3 us; no configuration that launches the variant was slower.  Nothing depends on the batch: a small grid fits one
+// residency round either way and executes the same vector instructions.
+inline int eval_waves_for(const rp_ctx *c) { return c->opt.eval_waves != 0 ? c->opt.eval_waves : 4; }
+
 template <int G, bool MAT, bool CIN, int COLL, bool STAGE>
 void launch_eval_tcs(rp_ctx *c, const KArgs &ka, int grid, size_t lds, int block = RP_BLOCK) {
     if constexpr (G == 16 && MAT && !STAGE) {   // rows of 64 doubles, no split tail (17 <= N + 1 <= 64, padded rows): the fixed-stride variant
         if (fixed_stride_applies(c, ka)) {
+            if (eval_waves_for(c) == 4) {
+                if (block == 64) launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, 64, false, true, true>, grid, 64, lds, ka);
+                else launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, RP_BLOCK, false, true, true>, grid, RP_BLOCK, lds, ka);
+                return;
+            }
             if (block == 64) launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, 64, false, true>, grid, 64, lds, ka);
             else launch_kargs(c, (const void *)rp_eval_kernel<G, MAT, CIN, COLL, false, false, false, RP_BLOCK, false, true>, grid, RP_BLOCK, lds, ka);
             return;
@@ -1045,7 +1066,7 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             if (which == 1) {
                 main_grid = (int)((count + RP_COST_BLOCK - 1) / RP_COST_BLOCK);
                 c->last_kernel = RP_KERNEL_COST;
-                c->last_fixed_stride = 0;
+                c->last_fixed_stride = c->last_eval_waves = 0;
                 const void *fn = k.low_vel_mode
                     ? (coll == 2 ? (const void *)rp_cost_kernel<true, 2> : coll == 1 ? (const void *)rp_cost_kernel<true, 1> : (const void *)rp_cost_kernel<true, 0>)
                     : (coll == 2 ? (const void *)rp_cost_kernel<false, 2> : coll == 1 ? (const void *)rp_cost_kernel<false, 1> : (const void *)rp_cost_kernel<false, 0>);
@@ -1053,12 +1074,13 @@ int pipeline_begin(rp_ctx *c, KArgs &ka, bool mat, bool cin, bool skip_eval, boo
             } else if (which == 2) {
                 main_grid = (int)((count + RP_CHUNK_BLOCK - 1) / RP_CHUNK_BLOCK);   // 64 candidates per workgroup, one wavefront per step block
                 c->last_kernel = RP_KERNEL_CHUNK;
-                c->last_fixed_stride = 0;
+                c->last_fixed_stride = c->last_eval_waves = 0;
                 launch_kargs(c, chunk_kernel_fn(k.low_vel_mode != 0, coll), main_grid, RP_CHUNK_BLOCK * chunk_G, rp_chunk_lds_bytes(chunk_G), k);
             } else {
                 main_grid = grid;
                 c->last_kernel = RP_KERNEL_EVAL;
                 c->last_fixed_stride = !fused_lds && mat_ && G == 16 && fixed_stride_applies(c, k);   // (as launch_eval_tcs decides)
+                c->last_eval_waves = c->last_fixed_stride ? eval_waves_for(c) : 3;
                 if (fused_lds) launch_eval_fused(c, k, grid, mat_, cin, fused_lds, G);
                 else launch_eval(c, k, grid, mat_, cin, G, block);
             }
@@ -1473,7 +1495,7 @@ int rp_set_option(rp_ctx *c, const char *key, int64_t value) {
     if (c->pending.active) return fail(c, RP_ESTATE, "rp_set_option: a plan is in flight on this context (rp_plan_wait first)");
     const OptionDesc *d = find_option(key);
     if (!d) return fail(c, RP_EINVAL, std::string("rp_set_option: unknown option '") + (key ? key : "(null)") + "'");
-    if (value < d->lo || value > d->hi) return fail(c, RP_EINVAL, std::string("rp_set_option: value out of range for '") + key + "'");
+    if (!option_value_ok(*d, value)) return fail(c, RP_EINVAL, std::string("rp_set_option: value out of range for '") + key + "'");
     c->opt.*(d->field) = (int)value;
     c->timing = c->opt.timing != 0;
     c->spin_wait = c->opt.wait_mode != RP_WAIT_EVENT;
@@ -1486,6 +1508,7 @@ int rp_get_option(const rp_ctx *c, const char *key, int64_t *value) {
     if (!c || !value) return RP_EINVAL;
     if (key && std::strcmp(key, "wait_fallbacks") == 0) { *value = c->wait_fallbacks; return RP_OK; }   // (read-only counter)
     if (key && std::strcmp(key, "last_fixed_stride") == 0) { *value = c->last_fixed_stride; return RP_OK; }   // (read-only: the last plan's batch)
+    if (key && std::strcmp(key, "last_eval_waves") == 0) { *value = c->last_eval_waves; return RP_OK; }       // (read-only: ... wavefronts per SIMD of its rp_eval_kernel instance, 4 | 3; 0: another kernel)
     if (key && std::strcmp(key, "last_lon_lean") == 0) { *value = c->last_lon_lean; return RP_OK; }           // (read-only: ... its profile launch was rp_lon_kernel's LEAN instance)
     if (key && std::strcmp(key, "last_collision_level") == 0) { *value = c->last_collision_level; return RP_OK; }   // (read-only: ... 0 no query, 1 dynamic table only, 2 static shapes as well)
     if (key && std::strcmp(key, "fold_static_steps") == 0) { *value = c->d_fold ? c->fold_steps : 0; return RP_OK; }   // (read-only: steps the folded table covers; 0: not built)

@@ -1170,8 +1170,9 @@ __device__ __forceinline__ void lateral_derivs(bool low, double dd, double ddd, 
 
 // orientations on the atan branch (reactive_planner.py:842-873): theta_cl = np.arctan2(dp, 1.0), theta_gl, and cos / sec / tan of
 // theta_cl, algebraic
+template <bool SC = false>   // SC: polynomial coefficients as scalar operands (rp_math.h: rp_fma3_sc), the same bits
 __device__ __forceinline__ void atan_angles(double dp, double th_ref, double &th_cl, double &th_gl, double &cosT, double &secT, double &tanT) {
-    th_cl = rp_atan(dp);
+    th_cl = rp_atan<SC>(dp);
     th_gl = th_cl + th_ref;
     const double w2 = __builtin_fma(dp, dp, 1.0);
     cosT = rp_rsqrt(w2);
@@ -1180,9 +1181,10 @@ __device__ __forceinline__ void atan_angles(double dp, double th_ref, double &th
 }
 
 // cos / sec / tan of theta_cl for the standstill lanes (!use_atan), once their th_cl holds the carried orientation (:866)
+template <bool SC = false>
 __device__ __forceinline__ void standstill_angles(double th_cl, bool use_atan, double &cosT, double &secT, double &tanT) {
     double sn, cs;
-    rp_sincos(th_cl, &sn, &cs);
+    rp_sincos<SC>(th_cl, &sn, &cs);
     const double sc = rp_rcp(cs);
     cosT = use_atan ? cosT : cs;
     secT = use_atan ? secT : sc;
@@ -1898,11 +1900,17 @@ __device__ __forceinline__ CandIn fetch_candidate(const KArgs &a, int64_t gidx, 
 // at immediate offsets from ONE address per lane, and the split-tail code is gone.  The host takes it by the layout (rp_host.hip:
 // launch_eval_tcs); the layout in device memory is the generic variant's.
 #define RP_ROW64 64
+// first set bit of a lane group's vote (m != 0).  NARROW (the four-wave instance, whose groups have 16 lanes: the vote fits 32 bits):
+// of the low word alone -- the 64-bit form leaves "first bit of the high word + 32" behind as a loop invariant, one more scalar
+// held across the step loop and spilled into a lane.
+template <bool NARROW>
+__device__ __forceinline__ int group_first(uint64_t m) { return NARROW ? __ffs((int)(uint32_t)m) - 1 : __ffsll((unsigned long long)m) - 1; }
 template <int G, bool MAT, bool COEFFS_IN, int COLL, bool ONE_CHUNK, bool STAGE_OUT, bool LON_FUSED, int BLOCK = RP_BLOCK, bool SWEEP = false,
-          bool ROW64 = false>
-__global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const KArgsG ag) {
+          bool ROW64 = false, bool W4 = false>
+__global__ __launch_bounds__(BLOCK, W4 ? 4 : RP_WAVES_PER_SIMD) void rp_eval_kernel(const KArgsG ag) {
     static_assert(!SWEEP || (G == 16 && !MAT && COLL != 0 && !STAGE_OUT && !LON_FUSED && BLOCK == RP_BLOCK), "the sweep's variant");
     static_assert(!ROW64 || (G == 16 && MAT && !ONE_CHUNK && !STAGE_OUT && !LON_FUSED && !SWEEP), "the fixed-stride variant");
+    static_assert(!W4 || ROW64, "four wavefronts per SIMD: an instance of the fixed-stride variant only");
     const KArgs &a = ag.k;
     extern __shared__ double lds_out[];   // STAGE_OUT: [groups per block][14][N+1];  LON_FUSED: tables, profiles, headers, votes
     static_assert(!(LON_FUSED && STAGE_OUT), "the single-launch variant stores state rows directly");
@@ -2311,7 +2319,11 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
             if (cp.has_speed) { asm volatile(""); e = v - cp.desired_speed; cst += 50.0 * (e * e); }
             if (cp.has_s) { asm volatile(""); e = 20.0 * (cp.desired_s - s); cst = __builtin_fma(e, e, cst); }
         }
-        if (i == mid && cp.has_speed) { asm volatile(""); e = v - cp.desired_speed; cst += 100.0 * (e * e); }
+        // (the four-wave instance forms n / 2 here, per step block, from a copy of n the compiler cannot see through: as a loop
+        //  invariant it is one of the scalars spilled into a lane before the step loop)
+        int mid_l = mid;
+        if (W4) { int nn = N; asm volatile("" : "+s"(nn)); mid_l = (nn + 1) / 2; }
+        if (i == mid_l && cp.has_speed) { asm volatile(""); e = v - cp.desired_speed; cst += 100.0 * (e * e); }
         return cst;
     };
 
@@ -2445,7 +2457,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     // -- orientations (:842-873) incl. the standstill carry of :866
                     const bool use_atan = moving || low;
                     double cosT, secT, tanT;
-                    atan_angles(dp, th_ref, th_cl, th_gl, cosT, secT, tanT);
+                    atan_angles<W4>(dp, th_ref, th_cl, th_gl, cosT, secT, tanT);
                     if (__any(act && !use_atan)) {   // standstill lanes: keep the orientation of the last moving step
                         const uint64_t mv = group_ballot<G>(use_atan && act, gbase);
                         const uint64_t below = mv & ((1ull << gl) - 1ull);
@@ -2455,7 +2467,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                             th_gl = below ? th_from : theta_carry;
                             th_cl = th_gl - th_ref;
                         }
-                        standstill_angles(th_cl, use_atan, cosT, secT, tanT);
+                        standstill_angles<W4>(th_cl, use_atan, cosT, secT, tanT);
                     }
                     // cos / sin of the heading theta = theta_ref + theta_cl from the profile's cos / sin of theta_ref (variants with a
                     // collision query; the others need them for one lane per candidate only, where the extension starts)
@@ -2479,7 +2491,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     reason = act ? reason : RP_REASON_NONE;
                     if (__any(reason != RP_REASON_NONE)) {   // wave-uniform
                         const uint64_t fm = group_ballot<G>(reason != RP_REASON_NONE, gbase);
-                        const int fl = fm ? __ffsll((unsigned long long)fm) - 1 : 0;
+                        const int fl = fm ? group_first<W4>(fm) : 0;
                         const uint32_t r_first = (uint32_t)__shfl((int)reason, fl, G);
                         if (fm && fail_step < 0) { fail_step = base + fl; fail_reason = r_first; }
                         if (!draw && fail_step >= 0) alive = false;
@@ -2492,7 +2504,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                     x = px + d * nx; y = py + d * ny;
                     if (__any(act && !in_dom) || ood_step >= 0) {   // wave-uniform ("ood_step" alone is group-uniform: harmless)
                         const uint64_t om = group_ballot<G>(act && !in_dom, gbase);
-                        if (om && ood_step < 0) ood_step = base + __ffsll((unsigned long long)om) - 1;
+                        if (om && ood_step < 0) ood_step = base + group_first<W4>(om);
                         if (ood_step >= 0 && i >= ood_step) { x = 0.0; y = 0.0; }   // x, y stay np.zeros past the break
                     }
                     if (act) {   // Cartesian rows of valid steps are final here
@@ -2524,7 +2536,7 @@ __global__ __launch_bounds__(BLOCK, RP_WAVES_PER_SIMD) void rp_eval_kernel(const
                 const int ll = L - 1 - base;
                 const bool take = (ll >= 0 && ll < G);     // this chunk holds the last valid state
                 if (__any(take && L < n)) {                // wave-uniform: park the last valid state in LDS
-                    if (!COLL) rp_sincos(th_gl, &sin_gl, &cos_gl);
+                    if (!COLL) rp_sincos<W4>(th_gl, &sin_gl, &cos_gl);
                     if (take && gl == ll) {
                         double *o = gs_last;
                         o[0] = x; o[1] = y; o[2] = th_gl; o[3] = v; o[4] = acc; o[5] = kappa; o[6] = kdot;

@@ -214,6 +214,11 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "stage_out", "row_padding", "row_align" (0 | 8 | 16), "tail_split"   RP_AMD_NO_STAGE_OUT, _NO_ROW_PADDING, _ROW_ALIGN, _NO_TAIL_SPLIT
  *   "fixed_stride"      RP_AMD_NO_FIXED_STRIDE      1 by layout | 0 never: fixed-stride variant of the 16-lane rp_eval_kernel that stores state
  *                                                   rows (rows of 64 doubles without a split tail: padded rows of 17 .. 64 steps)
+ *   "eval_waves"        RP_AMD_EVAL_WAVES           0 by policy | 3 | 4 (any other value: RP_EINVAL): which instance of the fixed-stride variant
+ *                                                   runs -- the one compiled for three wavefronts per SIMD (168 vector registers) or the one
+ *                                                   for four (128, polynomial coefficients as scalar operands).  Status words, cost bits and
+ *                                                   state rows are the same bits either way; launches that do not take the fixed-stride
+ *                                                   variant are not affected.
  *   "table_window", "lon_publish", "inline_grids", "zero_copy", "coeff_groups", "winner_skip_query"   RP_AMD_NO_<NAME>: 1 | 0
  *   "fold_static"       RP_AMD_FOLD_STATIC          -1 by rule | 0 never | 1 whenever the tables allow it: a few static rectangles are checked as
  *                                                   rows of the dynamic-obstacle table, so that the plan's kernels carry no static-shape
@@ -233,6 +238,8 @@ int rp_get_wait_mode(const rp_ctx *ctx);
  *   "wait_fallbacks"    (read-only, rp_get_option) waits for a completion ticket that ended in the 200-ms fall-back: 0 unless a kernel
  *                       chain failed to hand its ticket over
  *   "last_fixed_stride" (read-only, rp_get_option) 1: the batch of the last plan was evaluated by the fixed-stride variant
+ *   "last_eval_waves"   (read-only, rp_get_option) 4: ... by its four-wave instance ("eval_waves"), 3: by any other rp_eval_kernel
+ *                       instance, 0: the batch was evaluated by another kernel
  *   "last_lon_lean"     (read-only, rp_get_option) 1: the profile launch of the last plan was rp_lon_kernel's lean instance ("lean_broad"),
  *                       0: the other one, or the plan had no such launch (single-launch variant)
  *   "last_collision_level" (read-only, rp_get_option) 0 | 1 | 2: the kernels of the last plan ran without a collision query | against the
