@@ -2,3 +2,4 @@ from .trajectory_check import TrajectoryChecker, TrajectoryCheckResult  # noqa: 
 from .ensemble_check import EnsembleChecker, EnsembleCheckResult  # noqa: F401
 from .clearance import ClearanceQuery, ClearanceResult  # noqa: F401
 from .trajectory_score import TrajectoryScorer, TrajectoryScoreResult  # noqa: F401
+from .lift import TrajectoryLifter, TrajectoryLiftResult  # noqa: F401
