@@ -66,6 +66,8 @@ def lib() -> C.CDLL:
         _lib.rp_oracle_check_swept.argtypes = [C.POINTER(RpParams), C.POINTER(RpoTables), C.c_int, dp, dp, dp, dp]
         _lib.rp_oracle_obb_sum_rows.restype = None
         _lib.rp_oracle_obb_sum_rows.argtypes = [C.c_int, dp, dp]
+        _lib.rp_oracle_step_reasons.restype = None
+        _lib.rp_oracle_step_reasons.argtypes = [C.POINTER(RpParams), C.c_int, dp, dp, dp, dp, C.POINTER(C.c_uint8)]
         _lib.rpo_np_sum.restype = C.c_double
         _lib.rpo_np_sum.argtypes = [dp, C.c_long]
         _lib.rpo_quintic_coeffs.restype = None
@@ -184,6 +186,15 @@ def check_poses(params, tables: OracleTables, x, y, theta):
     tb = tables.c_struct()
     lib().rp_oracle_check_poses(C.byref(params), C.byref(tb), n, dptr(x), dptr(y), dptr(theta), hit.ctypes.data_as(C.POINTER(C.c_int32)))
     return hit.astype(bool), bool(hit.any())
+
+
+def step_reasons(params, v, kappa, theta, a) -> np.ndarray:
+    """``check_constraints`` at every step of one given trajectory under ``params.constraint_mask``: [n] uint8, the first failing
+    check of each step (0: none)."""
+    v, kappa, theta, a = f64(v), f64(kappa), f64(theta), f64(a)
+    out = np.zeros(len(v), dtype=np.uint8)
+    lib().rp_oracle_step_reasons(C.byref(params), len(v), dptr(v), dptr(kappa), dptr(theta), dptr(a), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
 
 
 def obb_sum_rows(dyn_obb) -> np.ndarray:

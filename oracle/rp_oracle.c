@@ -308,6 +308,13 @@ static unsigned check_constraints(const eval_env *e, const double *v, const doub
     return RP_REASON_NONE;
 }
 
+/* check_constraints at every step of one given trajectory: reason[i] = the first failing enabled check at step i (tests/_kin.py) */
+void rp_oracle_step_reasons(const rp_params *p, int n, const double *v, const double *kappa, const double *theta, const double *a,
+                            uint8_t *reason) {
+    eval_env e = {p, NULL, NULL, NULL, NULL, tan(p->delta_max) / p->wheelbase};
+    for (int i = 0; i < n; ++i) reason[i] = (uint8_t)check_constraints(&e, v, kappa, theta, a, i);
+}
+
 /* DefaultCostFunction.evaluate / DefaultCostFunctionFailSafe.evaluate,
  * commonroad_rp/cost_function.py:51-71, 82-92 (over the extended N+1 arrays). tmp: N+1 scratch */
 static double eval_cost(const rp_cost *c, int n, const double *st, double *tmp) {

@@ -32,6 +32,8 @@ int rp_oracle_check_swept(const rp_params *p, const rpo_tables *tb, int n, const
                           const double *theta, double *boxes);
 void rp_oracle_check_poses(const rp_params *p, const rpo_tables *tb, int n, const double *x, const double *y, const double *theta,
                            int32_t *hit);
+void rp_oracle_step_reasons(const rp_params *p, int n, const double *v, const double *kappa, const double *theta, const double *a,
+                            uint8_t *reason);
 void rp_oracle_obb_sum_rows(int n_steps, const double *rows, double *out);
 void rp_oracle_sample(const rp_params *p, const rp_grids *g, int64_t idx, double lon[6], double lat[6],
                       double *lat_T, int *traj_len);

@@ -375,6 +375,26 @@ def _evaluate(c, lon, lat, traj_len):
         s4 = s2 * s2
         s5 = s4 * s1
         d, d_vel, d_acc = z(_pos(ct, s1, s2, s3, s4, s5)), z(_vel(ct, s1, s2, s3, s4)), z(_acc(ct, s1, s2, s3))
+    return _from_planes(c, s, s_vel, s_acc, d, d_vel, d_acc, tl)
+
+
+def evaluate_planes(c: Case, planes, traj_len):
+    """evaluate() for GIVEN curvilinear planes s, s', s'', d, d', d'' ([m, n] doubles, read exactly; zero behind each length) in place of
+    polynomials: what a caller of the lift brings (tests/_kin_plan.py)"""
+    tl = np.minimum(np.asarray(traj_len), c.inp.params.N + 1).astype(np.int64)
+    valid = np.arange(c.inp.params.N + 1)[None, :] < tl[:, None]
+    with np.errstate(all="ignore"):
+        return _from_planes(c, *(dd.where(valid, _dd_in(q), 0) for q in planes), tl)
+
+
+def _from_planes(c, s, s_vel, s_acc, d, d_vel, d_acc, tl):
+    """reactive_planner.py:776-960 from the six curvilinear planes on"""
+    p, tb, cst = c.inp.params, c.tables, c.inp.cost
+    n, m = p.N + 1, len(tl)
+    dt = DD(LD(p.dt))
+    low = bool(p.low_vel_mode)
+    valid = np.arange(n)[None, :] < tl[:, None]
+    z = lambda a: dd.where(valid, a, 0)
     s_vel = dd.where(abs(s_vel) < DD(EPS), 0, s_vel)
     d_vel = dd.where(abs(d_vel) < DD(EPS), 0, d_vel)
     moving = s_vel > DD(S_VEL_MIN)
