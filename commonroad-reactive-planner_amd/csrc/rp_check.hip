@@ -12,74 +12,14 @@
 #include <string>
 #include <vector>
 
-#include "rp_device.h"
+#include "rp_check_rules.h"   // the tables' layout and builder, cc.collide and both tests of a chunk: shared with rp_pick.hip
 #include "../../include/rp_check.h"
 
 namespace {
 
 constexpr int CK_BLOCK = 256;                   // four wavefronts per workgroup
 constexpr int CK_WAVES = CK_BLOCK / 64;
-constexpr int CK_ROW = 10;                      // doubles per static row (below)
 constexpr int CK_LDS_ROWS = 128;                // static rows staged in LDS (10 KiB per workgroup); more: read from device memory
-constexpr int32_t CK_NONE = 0x7f7f7f7f;         // "no hit yet" of the first-hit arrays (a byte fill), above every pose index
-
-// Static shapes as ONE table, rectangles first, then triangles, then circles; every lane of a wavefront reads the same row
-// (a broadcast from LDS, or a scalar load).  Row: [0..5] the shape -- rectangle cx, cy, ux, uy, hl, hw | triangle x1 .. y3 |
-// circle cx, cy, r -- then [6..8] its bounding circle cx, cy, r and one double of padding.
-// Dynamic rectangles: struct-of-arrays planes [7][n_dyn][n_steps] cx, cy, ux, uy, hl, hw, r_bound (cx = NaN: absent), so that the
-// lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
-struct CkTables {
-    const double *stat;
-    const double *dyn;
-    int32_t n_sobb, n_tri, n_circ, n_dyn, n_steps, dyn_t0;
-};
-
-typedef const double __attribute__((address_space(3))) *lds_cdouble;
-
-// cc.collide(rectangle e at scenario time index t) for the lanes that `want` it.  Every lane of the wavefront calls this.
-// r: radius of a circle around e (bounding-circle rejection in front of every exact test; the small relative margin keeps it from
-// rejecting a pair the exact test would accept).  A lane stops at its first hit.
-template <bool LDS>
-__device__ __forceinline__ bool ck_collides(const CkTables &tb, const double *lds_rows, const Obb &e, double r, long long t, bool want) {
-    bool hit = false;
-    auto row = [&](int j, int q) -> double {
-        if constexpr (LDS) return ((lds_cdouble)lds_rows)[j * CK_ROW + q];
-        else return ((gcdouble)tb.stat)[(size_t)j * CK_ROW + q];
-    };
-    const int n_static = tb.n_sobb + tb.n_tri + tb.n_circ;
-    for (int j = 0; j < n_static; ++j) {   // wave-uniform
-        const double dx = row(j, 6) - e.cx, dy = row(j, 7) - e.cy, rr = r + row(j, 8);
-        if (want && !hit && dx * dx + dy * dy <= rr * rr * 1.000001) {   // false for NaN
-            if (j < tb.n_sobb) {
-                const Obb b = {row(j, 0), row(j, 1), row(j, 2), row(j, 3), row(j, 4), row(j, 5)};
-                hit = obb_obb(e, b);
-            } else if (j < tb.n_sobb + tb.n_tri) {
-                const double tv[6] = {row(j, 0), row(j, 1), row(j, 2), row(j, 3), row(j, 4), row(j, 5)};
-                hit = obb_tri(e, tv);
-            } else {
-                hit = obb_circ(e, row(j, 0), row(j, 1), row(j, 2));
-            }
-        }
-    }
-    // dynamic rectangles at the lane's own time index; outside the table: absent
-    const long long k = t - (long long)tb.dyn_t0;
-    const bool in_table = want && k >= 0 && k < (long long)tb.n_steps;
-    const size_t kc = in_table ? (size_t)k : 0;
-    const size_t plane = (size_t)tb.n_dyn * (size_t)tb.n_steps;
-    const gcdouble dyn = (gcdouble)tb.dyn;
-    for (int j = 0; j < tb.n_dyn; ++j) {
-        const bool open = in_table && !hit;
-        if (!__any(open)) break;   // the wavefront goes on while any lane is unresolved
-        const gcdouble o = dyn + (size_t)j * (size_t)tb.n_steps + kc;
-        const double cx = o[0], cy = o[plane], rr = r + o[6 * plane];
-        const double dx = cx - e.cx, dy = cy - e.cy;
-        if (open && dx * dx + dy * dy <= rr * rr * 1.000001) {   // false for NaN: absent
-            const Obb b = {cx, cy, o[2 * plane], o[3 * plane], o[4 * plane], o[5 * plane]};
-            hit = obb_obb(e, b);
-        }
-    }
-    return hit;
-}
 
 // A lane is a pose (and the segment that starts at it), a wavefront 64 consecutive poses of one trajectory: wavefront w of the
 // grid = chunk w % nchunk of trajectory w / nchunk.  poses: planes x | y | theta, each [K][n].  first_pose / first_seg hold CK_NONE
@@ -105,27 +45,16 @@ __global__ __launch_bounds__(CK_BLOCK) void rp_check_batch_kernel(CkTables tb, c
     const bool have = i < L;
     const size_t plane = (size_t)K * (size_t)n;
     const size_t at = (size_t)k * (size_t)n + (size_t)(have ? i : 0);   // lanes behind the end: pose 0, never asked
-    double s, c;
-    sincos(poses[2 * plane + at], &s, &c);
-    const Obb ego = {poses[at] + wb_rear_axle * c, poses[plane + at] + wb_rear_axle * s, c, s, hl, hw};
+    const Obb ego = ck_ego(poses, plane, at, wb_rear_axle, hl, hw);
 
     if (mode & RP_TRAJ_POSES) {
-        const bool hit = ck_collides<LDS>(tb, sh_rows, ego, sqrt(hl * hl + hw * hw), (long long)t0 + (long long)i * factor, have);
+        const bool hit = ck_pose_hit<LDS>(tb, sh_rows, ego, hl, hw, t0, factor, i, have);
         if (pose_hit && i < n) pose_hit[(size_t)k * (size_t)n + (size_t)i] = hit ? 1 : 0;
         const unsigned long long b = __ballot(hit);
         if (b != 0 && lane == 0) atomicMin(&first_pose[k], chunk * 64 + (__ffsll(b) - 1));
     }
     if (mode & RP_TRAJ_SWEPT) {
-        // the rectangle of pose i + 1 comes from the next lane; the wavefront's last lane loads that pose itself
-        const bool seg = i + 1 < L;
-        Obb nxt = {__shfl_down(ego.cx, 1), __shfl_down(ego.cy, 1), __shfl_down(ego.ux, 1), __shfl_down(ego.uy, 1), hl, hw};
-        if (lane == 63 && seg) {
-            double s1, c1;
-            sincos(poses[2 * plane + at + 1], &s1, &c1);
-            nxt.cx = poses[at + 1] + wb_rear_axle * c1; nxt.cy = poses[plane + at + 1] + wb_rear_axle * s1; nxt.ux = c1; nxt.uy = s1;
-        }
-        const Obb m = merge_swept(ego, seg ? nxt : ego);
-        const bool hit = ck_collides<LDS>(tb, sh_rows, m, sqrt(m.hl * m.hl + m.hw * m.hw), (long long)t0 + (long long)i, seg);
+        const bool hit = ck_segment_hit<LDS>(tb, sh_rows, ego, poses, plane, at, wb_rear_axle, hl, hw, t0, i, L, lane);
         const unsigned long long b = __ballot(hit);
         if (b != 0 && lane == 0) atomicMin(&first_seg[k], chunk * 64 + (__ffsll(b) - 1));
     }
@@ -235,46 +164,13 @@ int rp_checker_set_obstacles(rp_checker *ck, int32_t n_sobb, const double *sobb,
                              const double *circ, int32_t n_dyn, int32_t n_steps, int32_t dyn_t0, const double *dyn) {
     if (!ck) return RP_EINVAL;
     if (!ck->stream) return fail(ck, RP_ESTATE, "rp_checker_set_obstacles: the checker has no device (rp_checker_create failed)");
-    if (n_sobb < 0 || n_tri < 0 || n_circ < 0 || n_dyn < 0 || n_steps < 0 || (n_sobb && !sobb) || (n_tri && !tri) || (n_circ && !circ) ||
-        (n_dyn && n_steps && !dyn))
-        return fail(ck, RP_EINVAL, "rp_checker_set_obstacles: negative count or null table");
-    if ((int64_t)n_sobb + n_tri + n_circ > INT32_MAX / CK_ROW) return fail(ck, RP_EINVAL, "rp_checker_set_obstacles: too many static shapes");
+    std::vector<double> a, e;
+    std::string msg;
+    const int built = ck_build_tables("rp_checker_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
+    if (built != RP_OK) return fail(ck, built, msg);
     CK_TRY(ck, hipSetDevice(ck->device));
     CK_TRY(ck, hipStreamSynchronize(ck->stream));
-    std::vector<double> a, e;
-    try {
-        a.assign(((size_t)n_sobb + (size_t)n_tri + (size_t)n_circ) * CK_ROW, 0.0);
-        e.assign((size_t)7 * (size_t)n_dyn * (size_t)n_steps, 0.0);
-    } catch (const std::bad_alloc &) {
-        return fail(ck, RP_ENOMEM, "rp_checker_set_obstacles: host memory");
-    }
-    double *r = a.data();
-    for (int j = 0; j < n_sobb; ++j, r += CK_ROW) {   // (ux, uy from the host's cos / sin, as rp_set_obstacles)
-        const double *o = sobb + 5 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = std::cos(o[2]); r[3] = std::sin(o[2]); r[4] = o[3]; r[5] = o[4];
-        r[6] = o[0]; r[7] = o[1]; r[8] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    for (int j = 0; j < n_tri; ++j, r += CK_ROW) {
-        const double *o = tri + 6 * (size_t)j;
-        for (int q = 0; q < 6; ++q) r[q] = o[q];
-        const double bx = (o[0] + o[2] + o[4]) / 3.0, by = (o[1] + o[3] + o[5]) / 3.0;
-        double rr = 0.0;
-        for (int q = 0; q < 3; ++q) rr = std::fmax(rr, std::hypot(o[2 * q] - bx, o[2 * q + 1] - by));
-        r[6] = bx; r[7] = by; r[8] = rr;
-    }
-    for (int j = 0; j < n_circ; ++j, r += CK_ROW) {
-        const double *o = circ + 3 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
-        r[6] = o[0]; r[7] = o[1]; r[8] = o[2];
-    }
     const size_t plane = (size_t)n_dyn * (size_t)n_steps;
-    for (size_t at = 0; at < plane; ++at) {
-        const double *o = dyn + 5 * at;
-        e[at] = o[0]; e[plane + at] = o[1];
-        e[2 * plane + at] = std::cos(o[2]); e[3 * plane + at] = std::sin(o[2]);
-        e[4 * plane + at] = o[3]; e[5 * plane + at] = o[4];
-        e[6 * plane + at] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
     ck->tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};   // (a failed upload leaves empty tables, never half of the new ones)
     int rc;
     if ((rc = upload(ck, ck->d_stat, a)) != RP_OK) return rc;

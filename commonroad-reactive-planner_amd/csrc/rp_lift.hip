@@ -14,87 +14,15 @@
 #include <string>
 #include <vector>
 
-#include "rp_device.h"
-#include "rp_frontend.h"
+#include "rp_lift_rules.h"   // the segment row, the segment search, the step's checks: shared with rp_pick.hip
 #include "../../include/rp_lift.h"
 
 namespace {
 
 constexpr int LF_BLOCK = 256;                   // four wavefronts per workgroup
 constexpr int LF_WAVES = LF_BLOCK / 64;
-constexpr int LF_ROW = 16;                      // doubles per segment row (below)
 constexpr int LF_LDS_ROWS = 384;                // most segment rows staged in LDS (128 B each, 48 KiB); more: read from device memory
 constexpr int LF_FINAL_BLOCK = 1024;            // the one workgroup of rp_lift_final_kernel
-constexpr int LF_PLANES = 8;                    // x, y, theta, v, a, kappa, kappa_dot, theta_cl
-constexpr uint32_t LF_KEY_NONE = 0xFFFFFFFFu;   // a trajectory's verdict key (below): nothing failed
-constexpr uint32_t LF_KEY_LATE = 0x40000000u;   // ... |d| beyond the limit: behind every step's own failure
-
-// One row per segment:
-//   [0..1] p0   [2..3] e = p1 - p0   [4..5] t0   [6..7] dt = t1 - t0   [8] pos0   [9] pos1 - pos0   [10] theta0   [11] theta1 - theta0
-//   [12] curv0   [13] curv1 - curv0   [14] curv_d0   [15] curv_d1 - curv_d0
-enum { R_PX, R_PY, R_EX, R_EY, R_TX, R_TY, R_DTX, R_DTY, R_POS, R_DPOS, R_TH, R_DTH, R_KR, R_DKR, R_KRD, R_DKRD };
-
-typedef const double __attribute__((address_space(3))) *lds_cdouble;
-
-struct LfTable {
-    const double *rows;
-    int32_t n_seg, iters;   // iters: trips of the segment search, 2^iters >= n_seg + 1
-    double pos_first, pos_last, d_limit;
-};
-
-// what the step's checks and the standstill rule read besides the pose arrays
-struct LfKin {
-    uint32_t mask;
-    int32_t low_vel;
-    double dt, wheelbase, a_max, v_switch, v_delta_max, kappa_max, theta0;
-};
-
-template <bool LDS>
-struct LfRows {
-    const double *lds, *dev;
-    __device__ __forceinline__ double operator()(int k, int q) const {
-        if constexpr (LDS) return ((lds_cdouble)lds)[k * LF_ROW + q];
-        else return ((gcdouble)dev)[(size_t)k * LF_ROW + q];
-    }
-};
-
-// k = the last vertex with ref_pos[k] <= s, clamped to [0, n_seg - 1]: a binary search over the rows' pos0 with a fixed trip count
-// and no branch.  Whatever s is (NaN included) the result is a valid row.
-template <class Row>
-__device__ __forceinline__ int find_segment(const Row &row, int n_seg, int iters, double s) {
-    int lo = 0, hi = n_seg;   // the number of rows with pos0 <= s lies in [lo, hi]
-    for (int it = 0; it < iters; ++it) {   // wave-uniform
-        const int mid = (lo + hi) >> 1;
-        const bool open = lo < hi, le = row(mid < n_seg ? mid : n_seg - 1, R_POS) <= s;
-        lo = open && le ? mid + 1 : lo;
-        hi = open && !le ? mid : hi;
-    }
-    return lo > 0 ? lo - 1 : 0;
-}
-
-__device__ __forceinline__ bool lf_finite(double v) { return fabs(v) < __builtin_huge_val(); }   // (false for NaN)
-
-// _check_constraints at one step: the first failing check in the reference's order, or RP_REASON_NONE
-__device__ __forceinline__ uint32_t step_reason(const LfKin &kin, bool first, double v, double acc, double kappa, double kappa_prev, double theta,
-                                                double theta_prev) {
-    if ((kin.mask & RP_CHECK_VELOCITY) && v < -RP_EPS) return RP_REASON_VELOCITY;
-    if ((kin.mask & RP_CHECK_KAPPA) && fabs(kappa) > kin.kappa_max) return RP_REASON_KAPPA;
-    if (kin.mask & RP_CHECK_YAW_RATE) {
-        const double yaw = first ? 0.0 : (theta - theta_prev) / kin.dt;
-        if (fabs(rint(yaw * 1e5) / 1e5) > kin.kappa_max * v) return RP_REASON_YAW_RATE;   // round(yaw_rate, 5) of a float64
-    }
-    if (kin.mask & RP_CHECK_KAPPA_DOT) {
-        const double wk = kin.wheelbase * kappa;                                          // 1 / cos^2(atan(wk)) = 1 + wk^2
-        const double kd = first ? 0.0 : (kappa - kappa_prev) / kin.dt;
-        if (fabs(kd) > kin.v_delta_max * (1.0 + wk * wk) / kin.wheelbase) return RP_REASON_KAPPA_DOT;
-    }
-    if (kin.mask & RP_CHECK_ACCELERATION) {
-        const double hi = v > kin.v_switch ? kin.a_max * kin.v_switch / v : kin.a_max;
-        if (!(-kin.a_max <= acc && acc <= hi)) return RP_REASON_ACCELERATION;
-    }
-    return RP_REASON_NONE;
-}
-
 // Wavefront w of the grid = trajectory w; in chunk c its lane holds pose 64 c + lane.  in: the six planes s, s_dot, s_ddot, d,
 // d_dot, d_ddot, each [K][n]; out: the eight planes of LF_PLANES, each [K][n] (NaN from the pose that stops the trajectory and behind
 // its end); status [K].
@@ -113,97 +41,24 @@ __global__ __launch_bounds__(LF_BLOCK) void rp_lift_pose_kernel(LfTable tb, LfKi
     const LfRows<LDS> row = {sh_rows, tb.rows};
     const size_t P = (size_t)K * (size_t)n, base = (size_t)k * (size_t)n;
     const int L = len ? len[k] : n;           // 1 <= L <= n, checked by the host
-    const double nan = __builtin_nan("");
-    const uint64_t upto = lane == 63 ? ~0ull : (2ull << lane) - 1ull;   // the lanes up to and including this one
-    // what crosses a chunk boundary: the orientation a standstill keeps, theta and kappa of the chunk's last pose, and whether the
-    // trajectory was stopped
-    double keep = theta0 ? theta0[k] : kin.theta0, th_last = 0.0, kp_last = 0.0;
-    bool dead = false;
-    uint32_t best = LF_KEY_NONE;              // the lane's smallest step << 3 | reason
-    const int nchunk = (n + 63) / 64;
-    for (int c = 0; c < nchunk; ++c) {        // wave-uniform
-        const int i = c * 64 + lane;
-        if (c * 64 >= L || dead) {            // nothing but NaN from here on
-            if (i < n)
-#pragma unroll
-                for (int q = 0; q < LF_PLANES; ++q) out[(size_t)q * P + base + i] = nan;
-            continue;
-        }
-        const bool have = i < L;
-        const size_t at = base + (size_t)(have ? i : 0);   // lanes behind the end: pose 0, never used
-        const double s = in[at], sdd = in[2 * P + at], d = in[3 * P + at], ddd = in[5 * P + at];
-        double sd = in[P + at], dd = in[4 * P + at];
-        if (fabs(sd) < RP_EPS) sd = 0.0;
-        if (fabs(dd) < RP_EPS) dd = 0.0;
-        const bool on_s = lf_finite(s) && lf_finite(sd) && lf_finite(sdd) && lf_finite(d) && lf_finite(dd) && lf_finite(ddd) && s >= tb.pos_first && s <= tb.pos_last;
-        const bool off = have && !on_s;
-        const uint64_t offs = __ballot(off);
-        const bool before = (offs & upto & ~(1ull << lane)) != 0;   // an earlier pose of this chunk stopped the trajectory
-        const int seg = find_segment(row, tb.n_seg, tb.iters, s);
-        const double pos0 = row(seg, R_POS), dpos = row(seg, R_DPOS);
-        const double lam = (s - pos0) / dpos;
-        const double th_r = make_valid_orientation(row(seg, R_DTH) * (s - pos0) / dpos + row(seg, R_TH));   // interpolate_angle
-        const double kr = row(seg, R_DKR) * lam + row(seg, R_KR), krd = row(seg, R_DKRD) * lam + row(seg, R_KRD);
-        const bool moving = sd > 0.001;
-        double dp, dpp;
-        if (kin.low_vel) { dp = dd; dpp = ddd; }
-        else {
-            dp = moving ? dd / sd : 0.0;
-            dpp = moving ? (ddd - dp * sdd) / (sd * sd) : 0.0;
-        }
-        const bool stand = !kin.low_vel && !moving;
-        const double thcl_m = rp_atan(dp);
-        // The standstill carry: a pose at standstill takes theta of the last pose before it that defines its own -- a scan over the
-        // lanes for "the last flagged value" (the operator (a, b) -> b.flag ? b : a is associative), six shuffles; lanes without a
-        // flagged pose before them in this chunk take what the chunks before left.
-        double cv = thcl_m + th_r;
-        int cf = stand ? 0 : 1;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double tv = __shfl_up(cv, o);
-            const int tf = __shfl_up(cf, o);
-            if (lane >= o && !cf) { cv = tv; cf = tf; }
-        }
-        const double th = cf ? cv : keep;
-        const double thcl = stand ? th - th_r : thcl_m;
-        double sn, cs;
-        rp_sincos(thcl, &sn, &cs);
-        const double tn = sn / cs;
-        const double q = 1.0 - kr * d, cq = cs / q;
-        const double kp = (dpp + (kr * dp + krd * d) * tn) * cs * (cq * cq) + cq * kr;
-        const double v = sd * (q / cs);
-        const double a = sdd * q / cs + ((sd * sd) / cs) * (q * tn * (kp * q / cs - kr) - (krd * d + kr * dp));
-        // the step before: the neighbour lane's, lane 0 takes the last chunk's
-        double th_p = __shfl_up(th, 1), kp_p = __shfl_up(kp, 1);
-        if (lane == 0) { th_p = th_last; kp_p = kp_last; }
-        const bool first = i == 0;
-        const uint32_t code = step_reason(kin, first, v, a, kp, kp_p, th, th_p);
-        const bool in_d = fabs(d) <= tb.d_limit;
-        if (have && !before) {
-            const uint32_t key = off ? ((uint32_t)i << 3) | RP_REASON_OUT_OF_DOMAIN
-                                 : code ? ((uint32_t)i << 3) | code
-                                 : !in_d ? LF_KEY_LATE | ((uint32_t)i << 3) | RP_REASON_OUT_OF_DOMAIN : LF_KEY_NONE;
-            best = key < best ? key : best;
-        }
-        if (i < n) {
-            const bool gone = !have || before || off;
-            const double tx = row(seg, R_TX) + lam * row(seg, R_DTX), ty = row(seg, R_TY) + lam * row(seg, R_DTY), tl = sqrt(tx * tx + ty * ty);
-            const double px = row(seg, R_PX) + lam * row(seg, R_EX), py = row(seg, R_PY) + lam * row(seg, R_EY);
-            double *o = out + base + i;
-            o[0] = gone || !in_d ? nan : px - d * (ty / tl);
-            o[P] = gone || !in_d ? nan : py + d * (tx / tl);
-            o[2 * P] = gone ? nan : th;
-            o[3 * P] = gone ? nan : v;
-            o[4 * P] = gone ? nan : a;
-            o[5 * P] = gone ? nan : kp;
-            o[6 * P] = gone ? nan : (first ? 0.0 : kp - kp_p);
-            o[7 * P] = gone ? nan : thcl;
-        }
-        keep = __shfl(th, 63);
-        th_last = keep;
-        kp_last = __shfl(kp, 63);
-        dead = offs != 0;
+    // the walk itself is text shared with rp_pick.hip; here every pose goes to the eight planes at [k][i]
+#define LF_PUT_NAN(I) \
+    _Pragma("unroll") for (int q = 0; q < LF_PLANES; ++q) out[(size_t)q * P + base + (I)] = nan
+#define LF_PUT_POSE(I, X, Y, TH, V, A, KP, KPD, THCL, LIVE, S, D) \
+    {                                                              \
+        double *o = out + base + (I);                              \
+        o[0] = X;                                                  \
+        o[P] = Y;                                                  \
+        o[2 * P] = TH;                                             \
+        o[3 * P] = V;                                              \
+        o[4 * P] = A;                                              \
+        o[5 * P] = KP;                                             \
+        o[6 * P] = KPD;                                            \
+        o[7 * P] = THCL;                                           \
     }
+#include "rp_lift_walk.inc"
+#undef LF_PUT_NAN
+#undef LF_PUT_POSE
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const uint32_t ob = __shfl_xor(best, o);
@@ -394,48 +249,17 @@ int rp_lift_set_reference(rp_lift *lf, int32_t n, const double *ref_xy, const do
                           const double *ref_curv_d, double proj_domain_d_limit) {
     if (!lf) return RP_EINVAL;
     if (!lf->stream) return fail(lf, RP_ESTATE, "rp_lift_set_reference: the object has no device (rp_lift_create failed)");
-    if (n < 2 || !ref_xy || !ref_pos || !ref_theta || !ref_curv || !ref_curv_d) return fail(lf, RP_EINVAL, "rp_lift_set_reference: n < 2 or a null table");
-    if (!(proj_domain_d_limit > 0.0) || !std::isfinite(proj_domain_d_limit))
-        return fail(lf, RP_EINVAL, "rp_lift_set_reference: proj_domain_d_limit must be positive and finite");
-    for (int32_t i = 0; i < n; ++i)
-        if (!std::isfinite(ref_xy[2 * (size_t)i]) || !std::isfinite(ref_xy[2 * (size_t)i + 1]) || !std::isfinite(ref_pos[i]) || !std::isfinite(ref_theta[i]) ||
-            !std::isfinite(ref_curv[i]) || !std::isfinite(ref_curv_d[i]))
-            return fail(lf, RP_EINVAL, "rp_lift_set_reference: non-finite value at vertex " + std::to_string(i));
-    for (int32_t i = 0; i + 1 < n; ++i) {
-        if (!(ref_pos[i + 1] > ref_pos[i])) return fail(lf, RP_EINVAL, "rp_lift_set_reference: ref_pos is not strictly increasing at vertex " + std::to_string(i + 1));
-        if (ref_xy[2 * (size_t)i] == ref_xy[2 * (size_t)i + 2] && ref_xy[2 * (size_t)i + 1] == ref_xy[2 * (size_t)i + 3])
-            return fail(lf, RP_EINVAL, "rp_lift_set_reference: zero-length segment " + std::to_string(i));
-    }
+    std::vector<double> rows;
+    std::string msg;
+    const int built = lf_build_rows("rp_lift_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
+    if (built != RP_OK) return fail(lf, built, msg);
     LF_TRY(lf, hipSetDevice(lf->device));
     LF_TRY(lf, hipStreamSynchronize(lf->stream));
-    std::vector<double> rows;
-    std::vector<rpfe::Pt> ref, tan;
-    try {
-        ref.resize(n);
-        for (int32_t i = 0; i < n; ++i) ref[i] = {ref_xy[2 * (size_t)i], ref_xy[2 * (size_t)i + 1]};
-        tan = rpfe::vertex_tangents(ref);
-        rows.assign((size_t)(n - 1) * LF_ROW, 0.0);
-    } catch (const std::bad_alloc &) {
-        return fail(lf, RP_ENOMEM, "rp_lift_set_reference: host memory");
-    }
-    for (int32_t k = 0; k + 1 < n; ++k) {
-        double *r = rows.data() + (size_t)k * LF_ROW;
-        r[R_PX] = ref[k].x; r[R_PY] = ref[k].y; r[R_EX] = ref[k + 1].x - ref[k].x; r[R_EY] = ref[k + 1].y - ref[k].y;
-        r[R_TX] = tan[k].x; r[R_TY] = tan[k].y; r[R_DTX] = tan[k + 1].x - tan[k].x; r[R_DTY] = tan[k + 1].y - tan[k].y;
-        r[R_POS] = ref_pos[k]; r[R_DPOS] = ref_pos[k + 1] - ref_pos[k];
-        r[R_TH] = ref_theta[k]; r[R_DTH] = ref_theta[k + 1] - ref_theta[k];
-        r[R_KR] = ref_curv[k]; r[R_DKR] = ref_curv[k + 1] - ref_curv[k];
-        r[R_KRD] = ref_curv_d[k]; r[R_DKRD] = ref_curv_d[k + 1] - ref_curv_d[k];
-        for (int q = 0; q < LF_ROW; ++q)
-            if (!std::isfinite(r[q])) return fail(lf, RP_EINVAL, "rp_lift_set_reference: segment " + std::to_string(k) + " is not finite");
-    }
     lf->tb = {nullptr, 0, 0, 0.0, 0.0, 0.0};   // (a failed upload leaves no table, never half of the new one)
     if (lf->d_rows) { LF_TRY(lf, hipFree(lf->d_rows)); lf->d_rows = nullptr; }
     LF_TRY(lf, hipMalloc((void **)&lf->d_rows, rows.size() * sizeof(double)));
     LF_TRY(lf, hipMemcpy(lf->d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    int32_t iters = 0;
-    while (((int64_t)1 << iters) < (int64_t)n) ++iters;   // n = n_seg + 1 possible answers of the segment search
-    lf->tb = {lf->d_rows, n - 1, iters, ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
+    lf->tb = {lf->d_rows, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
     return RP_OK;
 }
 
