@@ -4,8 +4,8 @@
 // default cost of rp_score.h, the collision tests of rp_check.h and ReactivePlanner._get_optimal_trajectory's choice among them, with
 // the poses staying on the device between the stages.  The mapping is the family's: a lane is a pose, a wavefront 64 consecutive
 // poses of one trajectory, a workgroup four wavefronts.  The per-pose lift step and the obstacle walk are the two siblings', from
-// the files they are stated in once (rp_lift_rules.h with rp_lift_walk.inc, rp_check_rules.h).  What is written here is the cost, the
-// skip of infeasible trajectories, the final stage and the host side.
+// the files they are stated in once (rp_lift_rules.h with rp_lift_walk.inc, rp_check_rules.h), and the cost is stated in
+// rp_pick_cost.h, for rp_epick.hip too.  What is written here is the skip of infeasible trajectories, the final stage and the host side.
 //
 //   rp_pick_lift_kernel      one wavefront walks one trajectory: eight planes (x, y, theta always, the rest where asked for), the
 //                            kinematic verdict and the cost
@@ -22,6 +22,7 @@
 
 #include "rp_check_rules.h"   // the obstacle tables, cc.collide and both tests of a chunk: shared with rp_check.hip
 #include "rp_lift_rules.h"    // the segment row, the segment search, the step's checks: shared with rp_lift.hip
+#include "rp_pick_cost.h"     // the cost's scalars and the terms of a pose: shared with rp_epick.hip
 #include "../../include/rp_pick.h"
 
 namespace {
@@ -39,13 +40,6 @@ enum { RED_BEST, RED_COST, RED_FEASIBLE, RED_COLLISION, RED_BEFORE, RED_REASON0 
 // the row of a state block each of the eight planes and each of the six input planes is
 constexpr int PK_PLANE_ROW[LF_PLANES] = {RP_X, RP_Y, RP_THETA, RP_V, RP_A, RP_KAPPA, RP_KAPPA_DOT, RP_THETA_CL};
 constexpr int PK_INPUT_ROW[6] = {RP_S, RP_S_DOT, RP_S_DDOT, RP_D, RP_D_DOT, RP_D_DDOT};
-
-// cost_function.py:51-71, 82-92 as rp_score.hip holds it: the fail-safe cost is the default one with w_a = 1, desired_d = 0 and no
-// v / s terms
-struct PkCost {
-    int32_t has_speed, has_s;
-    double w_a, desired_speed, desired_d, desired_s;
-};
 
 // where a launch writes each of the eight planes (nullptr: nowhere)
 struct PkPlanes {
@@ -89,22 +83,7 @@ __global__ __launch_bounds__(PK_BLOCK) void rp_pick_lift_kernel(LfTable tb, LfKi
     const int L = len ? len[k] : n;         // 1 <= L <= n, checked by the host
     const int last = L - 1, mid = L / 2;
     double sum = 0.0;
-    auto add_cost = [&](int i, double vel, double acc, double thcl, double s, double d) {
-        const double th = fabs(thcl);
-        double e;
-        e = cc.w_a * acc; sum += e * e;
-        e = 0.25 * (cc.desired_d - d); sum += e * e;
-        e = 0.25 * th; sum += e * e;
-        if (cc.has_speed) { e = 5.0 * (vel - cc.desired_speed); sum += e * e; }
-        if (cc.has_s) { e = 0.25 * (cc.desired_s - s); sum += e * e; }
-        if (i == last) {
-            e = 20.0 * (cc.desired_d - d); sum += e * e;
-            e = 5.0 * th; sum += e * e;
-            if (cc.has_speed) { e = vel - cc.desired_speed; sum += 50.0 * (e * e); }
-            if (cc.has_s) { e = 20.0 * (cc.desired_s - s); sum += e * e; }
-        }
-        if (i == mid && cc.has_speed) { e = vel - cc.desired_speed; sum += 100.0 * (e * e); }
-    };
+    const PkAddCost add_cost = {cc, sum, last, mid};
     // the walk itself is text shared with rp_lift.hip; here a pose goes to the planes this launch has a place for, and into the cost
 #define LF_PUT_NAN(I)                            \
     _Pragma("unroll") for (int pl = 0; pl < LF_PLANES; ++pl) \
@@ -483,10 +462,7 @@ int rp_pick_select(rp_pick *pk, const rp_params *p, const rp_cost *cost, uint32_
     const double *d_th0 = theta0 ? reinterpret_cast<const double *>(d_in + th0_off) : nullptr;
     const LfKin kin = {p->constraint_mask, p->low_vel_mode ? 1 : 0, p->dt, p->wheelbase, p->a_max, p->v_switch, p->v_delta_max,
                        std::tan(p->delta_max) / p->wheelbase, p->x0_orientation};
-    const bool failsafe = cost->kind == RP_COST_FAILSAFE;
-    const bool has_speed = !failsafe && !std::isnan(cost->desired_speed), has_s = !failsafe && !std::isnan(cost->desired_s);
-    const PkCost cc = {has_speed ? 1 : 0, has_s ? 1 : 0, failsafe ? 1.0 : cost->w_a, has_speed ? cost->desired_speed : 0.0, failsafe ? 0.0 : cost->desired_d,
-                       has_s ? cost->desired_s : 0.0};
+    const PkCost cc = pk_cost_of(cost);
     PkPlanes all;
     for (int q = 0; q < LF_PLANES; ++q) all.plane[q] = q < 3 || outs[q] ? d_planes + (size_t)q * P : nullptr;
     const bool rows_in_lds = pk->tb.n_seg <= PK_LF_LDS_ROWS;
