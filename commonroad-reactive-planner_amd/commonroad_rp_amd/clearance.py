@@ -13,17 +13,17 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import math
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpParams, dptr
+from ._session import as_ip
 
 __all__ = ["ClearanceQuery", "ClearanceResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_clearance.so")
+LIB_PATH = _session.lib_path("librp_clearance.so")
 ABI_VERSION = 1
 MAX_POSES = 1 << 24
 RP_X, RP_Y, RP_THETA, RP_N_ARRAYS = 0, 1, 2, 14   # rows of a state block (include/rp_amd.h)
@@ -41,34 +41,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_clearance.so`` and declare every entry point of ``include/rp_clearance.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_clearance_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_clearance_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -87,49 +63,14 @@ class ClearanceResult:
     best: int
 
 
-class ClearanceQuery:
+class ClearanceQuery(_session.Session):
     """Owner of one ``rp_clearance`` (one HIP stream, obstacle tables, pose and result buffers)."""
 
-    def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_clearance_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_clearance_last_error(self._h) if self._h else b"rp_clearance_create failed"
-            self.close()
-            raise RpError(f"rp_clearance_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_clearance_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_clearance_last_error(self._h) or b'').decode()}")
+    _prefix, _load = "rp_clearance", staticmethod(load_library)
 
     def set_obstacles(self, tables=None):
         """The tables ``RpContext.set_obstacles`` takes (``ObstacleTables``; None: empty); they replace the earlier ones."""
-        from .collision import ObstacleTables
-        tb = tables if tables is not None else ObstacleTables()
-        nd, ns = tb.dyn_obb.shape[0], tb.dyn_obb.shape[1]
-        self._check(self._lib.rp_clearance_set_obstacles(
-            self._h, len(tb.static_obb), dptr(tb.static_obb), len(tb.static_tri), dptr(tb.static_tri),
-            len(tb.static_circ), dptr(tb.static_circ), nd, ns, int(tb.dyn_t0), dptr(tb.dyn_obb)), "rp_clearance_set_obstacles")
+        self._set_obstacles(tables)
 
     def query(self, params: RpParams, x, y, theta, lengths=None, cutoff: float = math.inf, margin: float = 0.0,
               want_pose_clearance: bool = False) -> ClearanceResult:
@@ -137,24 +78,15 @@ class ClearanceQuery:
         trajectory (None: n).  Pose i is measured against the static shapes and the dynamic obstacles at time index
         ``time_step0 + i * factor``.  ``cutoff``: clearances above it are reported as +inf (and cost little); ``margin``: what
         ``first_clear`` and ``n_below`` compare with.  ``params``: what ``_capi.make_params`` returns."""
-        x, y, theta = (np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a) for a in (x, y, theta))
-        if not (x.ndim == y.ndim == theta.ndim == 2 and x.shape == y.shape == theta.shape):
-            raise ValueError(f"query: x, y, theta differ in shape ({x.shape}, {y.shape}, {theta.shape}) or are not [K, n]")
+        x, y, theta = _session.poses("query", x, y, theta)
         K, n = x.shape
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"query: {lens.shape[0]} lengths for {K} trajectories")
+        lens = _session.lengths_of("query", lengths, K)
         pose_clear = np.empty((K, n), dtype=np.float64) if want_pose_clearance else None
         min_clear = np.empty(K, dtype=np.float64)
         min_pose, nearest = np.empty(K, dtype=np.int32), np.empty(K, dtype=np.int32)
         first_clear, n_below, best = C.c_int64(-1), C.c_int64(0), C.c_int64(-1)
-        self._check(self._lib.rp_clearance_query(
-            self._h, C.byref(params), K, n, dptr(x), dptr(y), dptr(theta), lens.ctypes.data_as(_ip) if lens is not None else None,
-            float(cutoff), float(margin), pose_clear.ctypes.data_as(_dp) if pose_clear is not None else None, min_clear.ctypes.data_as(_dp),
-            min_pose.ctypes.data_as(_ip), nearest.ctypes.data_as(_ip), C.byref(first_clear), C.byref(n_below), C.byref(best)),
-            "rp_clearance_query")
+        self._call("query", C.byref(params), K, n, dptr(x), dptr(y), dptr(theta), as_ip(lens), float(cutoff), float(margin), dptr(pose_clear),
+                   dptr(min_clear), as_ip(min_pose), as_ip(nearest), C.byref(first_clear), C.byref(n_below), C.byref(best))
         return ClearanceResult(pose_clear, min_clear, min_pose, nearest, int(first_clear.value), int(n_below.value), int(best.value))
 
     def query_states(self, params: RpParams, states, lengths=None, **kw) -> ClearanceResult:

@@ -13,17 +13,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpParams, dptr
+from ._session import as_ip
 
 __all__ = ["EnsembleChecker", "EnsembleCheckResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_ensemble.so")
+LIB_PATH = _session.lib_path("librp_ensemble.so")
 ABI_VERSION = 1
 TRAJ_POSES, TRAJ_SWEPT = 1, 2
 MAX_MEMBERS = 4096
@@ -44,34 +44,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_ensemble.so`` and declare every entry point of ``include/rp_ensemble.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_ensemble_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_ensemble_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -86,61 +62,25 @@ class EnsembleCheckResult:
     n_over: int
 
 
-class EnsembleChecker:
+class EnsembleChecker(_session.Session):
     """Owner of one ``rp_ensemble`` (one HIP stream, static shapes, member tables, pose and result buffers)."""
 
+    _prefix, _load = "rp_ensemble", staticmethod(load_library)
+
     def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_ensemble_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_ensemble_last_error(self._h) if self._h else b"rp_ensemble_create failed"
-            self.close()
-            raise RpError(f"rp_ensemble_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
+        super().__init__(device, library)
         self.n_members = 1
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_ensemble_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_ensemble_last_error(self._h) or b'').decode()}")
 
     def set_static(self, tables=None):
         """The static shapes of an ``ObstacleTables`` (None: none); they replace the earlier ones, the members stay."""
-        from .collision import ObstacleTables
-        tb = tables if tables is not None else ObstacleTables()
-        self._check(self._lib.rp_ensemble_set_static(
-            self._h, len(tb.static_obb), dptr(tb.static_obb), len(tb.static_tri), dptr(tb.static_tri),
-            len(tb.static_circ), dptr(tb.static_circ)), "rp_ensemble_set_static")
+        self._set_static(tables)
 
     def set_members(self, members, dyn_t0: int = 0):
         """``members``: [M, n_dyn, n_steps, 5] dynamic rectangles (rows of ``ObstacleTables.dyn_obb``, cx = NaN: absent) for
-        scenario time steps ``dyn_t0 ..``; they replace the earlier members, the static shapes stay."""
-        mem = f64(members)
-        if mem.ndim != 4 or mem.shape[3] != 5:
-            raise ValueError(f"set_members: members must be [M, n_dyn, n_steps, 5], got {mem.shape}")
-        M, nd, ns = mem.shape[:3]
-        rc = self._lib.rp_ensemble_set_members(self._h, M, nd, ns, int(dyn_t0), dptr(mem) if mem.size else None)
-        if rc not in (0, -1):
-            self.n_members = 1   # (a failed upload leaves one member without dynamic obstacles; a refused argument the earlier members)
-        self._check(rc, "rp_ensemble_set_members")
+        scenario time steps ``dyn_t0 ..``; they replace the earlier members, the static shapes stay; a call that fails leaves the
+        earlier members."""
+        mem, M, nd, ns = _session.members_args(members)
+        self._call("set_members", M, nd, ns, int(dyn_t0), dptr(mem) if mem.size else None)
         self.n_members = M
 
     def set_obstacles(self, tables=None, members=None, dyn_t0: Optional[int] = None):
@@ -159,23 +99,15 @@ class EnsembleChecker:
         """``x``, ``y``, ``theta``: [K, n] rear-axle poses (one trajectory may come as 1-D); ``lengths``: [K] valid poses per
         trajectory (None: n).  ``poses``: the per-pose test at time index ``time_step0 + i * factor``; ``swept``: the continuous
         test of segment i at ``time_step0 + i``.  ``params``: what ``_capi.make_params`` returns."""
-        x, y, theta = (np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a) for a in (x, y, theta))
-        if not (x.ndim == y.ndim == theta.ndim == 2 and x.shape == y.shape == theta.shape):
-            raise ValueError(f"check: x, y, theta differ in shape ({x.shape}, {y.shape}, {theta.shape}) or are not [K, n]")
+        x, y, theta = _session.poses("check", x, y, theta)
         K, n = x.shape
         M = self.n_members
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"check: {lens.shape[0]} lengths for {K} trajectories")
+        lens = _session.lengths_of("check", lengths, K)
         mode = (TRAJ_POSES if poses else 0) | (TRAJ_SWEPT if swept else 0)
         first_pose = np.empty((K, M), dtype=np.int32) if poses else None
         first_seg = np.empty((K, M), dtype=np.int32) if swept else None
         members_hit = np.zeros(K, dtype=np.int32)
         first_free, n_over = C.c_int64(-1), C.c_int64(0)
-        as_ip = lambda a: a.ctypes.data_as(_ip) if a is not None else None   # noqa: E731
-        self._check(self._lib.rp_ensemble_check(
-            self._h, C.byref(params), mode, K, n, dptr(x), dptr(y), dptr(theta), as_ip(lens), int(max_members_hit), as_ip(first_pose),
-            as_ip(first_seg), as_ip(members_hit), C.byref(first_free), C.byref(n_over)), "rp_ensemble_check")
+        self._call("check", C.byref(params), mode, K, n, dptr(x), dptr(y), dptr(theta), as_ip(lens), int(max_members_hit), as_ip(first_pose),
+                   as_ip(first_seg), as_ip(members_hit), C.byref(first_free), C.byref(n_over))
         return EnsembleCheckResult(first_pose, first_seg, members_hit, int(first_free.value), int(n_over.value))

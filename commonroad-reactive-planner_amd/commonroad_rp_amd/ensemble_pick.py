@@ -14,17 +14,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpCost, RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpCost, RpParams, dptr, f64
+from ._session import as_ip
 
 __all__ = ["EnsemblePicker", "EnsemblePickResult", "RpEpickResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_epick.so")
+LIB_PATH = _session.lib_path("librp_epick.so")
 ABI_VERSION = 1
 TRAJ_POSES, TRAJ_SWEPT = 1, 2
 MAX_MEMBERS = 4096
@@ -61,34 +61,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_epick.so`` and declare every entry point of ``include/rp_epick.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_epick_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_epick_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -136,90 +112,36 @@ class EnsemblePickResult:
         return (self.status >> 8) & 0xFFF
 
 
-def _plane(a, shape, name):
-    a = np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a)
-    if a.shape != shape:
-        raise ValueError(f"pick: {name} of shape {a.shape}, s of shape {shape}")
-    return a
-
-
-class EnsemblePicker:
+class EnsemblePicker(_session.Session):
     """Owner of one ``rp_epick`` (one HIP stream, the segment table of one reference path, static shapes, member tables and weights,
     input and result buffers)."""
 
+    _prefix, _load = "rp_epick", staticmethod(load_library)
+
     def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_epick_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_epick_last_error(self._h) if self._h else b"rp_epick_create failed"
-            self.close()
-            raise RpError(f"rp_epick_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
+        super().__init__(device, library)
         self.n_members = 1
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_epick_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_epick_last_error(self._h) or b'').decode()}")
 
     def set_reference(self, ref_xy, ref_pos=None, ref_theta=None, ref_curv=None, ref_curv_d=None, d_limit: Optional[float] = None):
         """The arguments of ``TrajectoryPicker.set_reference``: the tables of ``rp_build_reference`` or the package's
         ``CoordinateSystem`` alone.  Replaces the earlier table."""
-        if ref_pos is None and hasattr(ref_xy, "ref_pos"):
-            co = ref_xy
-            ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = co.reference, co.ref_pos, co.ref_theta, co.ref_curv, co.ref_curv_d
-            if d_limit is None:
-                d_limit = co.proj_domain_d_limit
-        if ref_pos is None or ref_theta is None or ref_curv is None or ref_curv_d is None:
-            raise ValueError("set_reference: ref_xy, ref_pos, ref_theta, ref_curv and ref_curv_d, or a CoordinateSystem")
-        ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = f64(ref_xy), f64(ref_pos), f64(ref_theta), f64(ref_curv), f64(ref_curv_d)
-        n = ref_pos.shape[0]
-        if ref_xy.shape != (n, 2) or any(q.shape != (n,) for q in (ref_pos, ref_theta, ref_curv, ref_curv_d)):
-            raise ValueError(f"set_reference: shapes {ref_xy.shape}, {ref_pos.shape}, {ref_theta.shape}, {ref_curv.shape}, {ref_curv_d.shape}, "
-                             f"not [n, 2] and four times [n]")
-        self._check(self._lib.rp_epick_set_reference(self._h, n, dptr(ref_xy), dptr(ref_pos), dptr(ref_theta), dptr(ref_curv), dptr(ref_curv_d),
-                                                     20.0 if d_limit is None else float(d_limit)), "rp_epick_set_reference")
+        self._set_reference(ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, d_limit)
 
     def set_static(self, obs=None):
         """The static shapes of an ``ObstacleTables`` (None: none); they replace the earlier ones, the members stay."""
-        from .collision import ObstacleTables
-        tb = obs if obs is not None else ObstacleTables()
-        self._check(self._lib.rp_epick_set_static(
-            self._h, len(tb.static_obb), dptr(tb.static_obb), len(tb.static_tri), dptr(tb.static_tri),
-            len(tb.static_circ), dptr(tb.static_circ)), "rp_epick_set_static")
+        self._set_static(obs)
 
     def set_members(self, members, dyn_t0: int = 0, weights=None):
         """``members``: [M, n_dyn, n_steps, 5] dynamic rectangles (rows of ``ObstacleTables.dyn_obb``, cx = NaN: absent) for scenario
         time steps ``dyn_t0 ..``; ``weights``: [M] what each member adds to the risk of a trajectory that collides in it (None: 1.0
         each).  They replace the earlier members and weights, the static shapes stay; a refused call leaves the earlier ones."""
-        mem = f64(members)
-        if mem.ndim != 4 or mem.shape[3] != 5:
-            raise ValueError(f"set_members: members must be [M, n_dyn, n_steps, 5], got {mem.shape}")
-        M, nd, ns = mem.shape[:3]
+        mem, M, nd, ns = _session.members_args(members)
         w = None
         if weights is not None:
             w = f64(weights).reshape(-1)
             if w.shape[0] != M:
                 raise ValueError(f"set_members: {w.shape[0]} weights for {M} members")
-        self._check(self._lib.rp_epick_set_members(self._h, M, nd, ns, int(dyn_t0), dptr(mem) if mem.size else None, dptr(w)), "rp_epick_set_members")
+        self._call("set_members", M, nd, ns, int(dyn_t0), dptr(mem) if mem.size else None, dptr(w))
         self.n_members = M
 
     def pick(self, params: RpParams, cost: RpCost, s, s_dot, s_ddot, d, d_dot, d_ddot, lengths=None, theta0=None, poses: bool = True,
@@ -227,21 +149,10 @@ class EnsemblePicker:
         """The six planes, ``lengths``, ``theta0``, ``poses``, ``swept``, ``want_planes`` and ``params``, ``cost`` as in
         ``TrajectoryPicker.pick``; ``max_risk``: the bound (``inf`` accepts everything kinematically feasible); ``want_hits``: the
         [K, M] first-hit matrices of the requested tests come back."""
-        s = np.atleast_2d(f64(s)) if np.ndim(s) != 2 else f64(s)
+        s, s_dot, s_ddot, d, d_dot, d_ddot = _session.six_planes("pick", s, s_dot, s_ddot, d, d_dot, d_ddot)
         K, n = s.shape
         M = self.n_members
-        s_dot, s_ddot = _plane(s_dot, (K, n), "s_dot"), _plane(s_ddot, (K, n), "s_ddot")
-        d, d_dot, d_ddot = _plane(d, (K, n), "d"), _plane(d_dot, (K, n), "d_dot"), _plane(d_ddot, (K, n), "d_ddot")
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"pick: {lens.shape[0]} lengths for {K} trajectories")
-        th0 = None
-        if theta0 is not None:
-            th0 = f64(theta0).reshape(-1)
-            if th0.shape[0] != K:
-                raise ValueError(f"pick: {th0.shape[0]} orientations for {K} trajectories")
+        lens, th0 = _session.lengths_of("pick", lengths, K), _session.theta0_of("pick", theta0, K)
         mode = (TRAJ_POSES if poses else 0) | (TRAJ_SWEPT if swept else 0)
         planes = [np.empty((K, n)) if want_planes else None for _ in PLANES]
         status, costs = np.empty(K, dtype=np.uint32), np.empty(K)
@@ -250,11 +161,9 @@ class EnsemblePicker:
         first_seg = np.empty((K, M), dtype=np.int32) if want_hits and swept else None
         res = RpEpickResult()
         block = np.empty((RP_N_ARRAYS, n))
-        as_ip = lambda a: a.ctypes.data_as(_ip) if a is not None else None   # noqa: E731
-        self._check(self._lib.rp_epick_select(
-            self._h, C.byref(params), C.byref(cost), mode, float(max_risk), K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot),
-            dptr(d_ddot), as_ip(lens), dptr(th0), 0, *[dptr(q) for q in planes], status.ctypes.data_as(_up), dptr(costs), as_ip(members_hit),
-            dptr(risk), as_ip(first_pose), as_ip(first_seg), C.byref(res), dptr(block)), "rp_epick_select")
+        self._call("select", C.byref(params), C.byref(cost), mode, float(max_risk), K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot),
+                   dptr(d_ddot), as_ip(lens), dptr(th0), 0, *[dptr(q) for q in planes], status.ctypes.data_as(_up), dptr(costs), as_ip(members_hit),
+                   dptr(risk), as_ip(first_pose), as_ip(first_seg), C.byref(res), dptr(block))
         return EnsemblePickResult(status, costs, int(res.best), float(res.best_cost), block if res.best >= 0 else None, int(res.n_feasible),
                                   int(res.n_collision), int(res.n_collision_before_best), np.array(res.reason_counts[:], dtype=np.int64),
                                   *planes, first_pose, first_seg, members_hit, risk, int(res.best_members_hit), float(res.best_risk))

@@ -13,17 +13,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpParams, dptr, f64
+from ._session import as_ip
 
 __all__ = ["TrajectoryLifter", "TrajectoryLiftResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_lift.so")
+LIB_PATH = _session.lib_path("librp_lift.so")
 ABI_VERSION = 1
 MAX_POSES = 1 << 24
 # rows of a state block (include/rp_amd.h)
@@ -42,34 +42,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_lift.so`` and declare every entry point of ``include/rp_lift.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_lift_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_lift_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -104,66 +80,16 @@ class TrajectoryLiftResult:
         return (self.status >> 8) & 0xFFF
 
 
-def _plane(a, shape, name):
-    a = np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a)
-    if a.shape != shape:
-        raise ValueError(f"lift: {name} of shape {a.shape}, s of shape {shape}")
-    return a
-
-
-class TrajectoryLifter:
+class TrajectoryLifter(_session.Session):
     """Owner of one ``rp_lift`` (one HIP stream, the segment table of one reference path, input and result buffers)."""
 
-    def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_lift_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_lift_last_error(self._h) if self._h else b"rp_lift_create failed"
-            self.close()
-            raise RpError(f"rp_lift_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_lift_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_lift_last_error(self._h) or b'').decode()}")
+    _prefix, _load = "rp_lift", staticmethod(load_library)
 
     def set_reference(self, ref_xy, ref_pos=None, ref_theta=None, ref_curv=None, ref_curv_d=None, d_limit: Optional[float] = None):
         """The tables of ``rp_build_reference``: vertices [n, 2], arc lengths, unwrapped orientations, curvature and its derivative,
         [n] each; or the package's ``CoordinateSystem`` alone (its projection-domain limit unless ``d_limit`` is given).  Replaces the
         earlier table."""
-        if ref_pos is None and hasattr(ref_xy, "ref_pos"):
-            co = ref_xy
-            ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = co.reference, co.ref_pos, co.ref_theta, co.ref_curv, co.ref_curv_d
-            if d_limit is None:
-                d_limit = co.proj_domain_d_limit
-        if ref_pos is None or ref_theta is None or ref_curv is None or ref_curv_d is None:
-            raise ValueError("set_reference: ref_xy, ref_pos, ref_theta, ref_curv and ref_curv_d, or a CoordinateSystem")
-        ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = f64(ref_xy), f64(ref_pos), f64(ref_theta), f64(ref_curv), f64(ref_curv_d)
-        n = ref_pos.shape[0]
-        if ref_xy.shape != (n, 2) or any(q.shape != (n,) for q in (ref_pos, ref_theta, ref_curv, ref_curv_d)):
-            raise ValueError(f"set_reference: shapes {ref_xy.shape}, {ref_pos.shape}, {ref_theta.shape}, {ref_curv.shape}, {ref_curv_d.shape}, "
-                             f"not [n, 2] and four times [n]")
-        self._check(self._lib.rp_lift_set_reference(self._h, n, dptr(ref_xy), dptr(ref_pos), dptr(ref_theta), dptr(ref_curv), dptr(ref_curv_d),
-                                                    20.0 if d_limit is None else float(d_limit)), "rp_lift_set_reference")
+        self._set_reference(ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, d_limit)
 
     def points(self, s, d, want_outside: bool = False):
         """(x, y, segment) of a batch of curvilinear points, in the shape of ``s``: NaN, NaN, -1 off the path.  With ``want_outside``
@@ -173,8 +99,7 @@ class TrajectoryLifter:
             raise ValueError(f"points: s of shape {s.shape}, d of shape {d.shape}")
         x, y, seg = np.empty(s.shape), np.empty(s.shape), np.empty(s.shape, dtype=np.int32)
         n_out = C.c_int64(0)
-        self._check(self._lib.rp_lift_points(self._h, s.size, dptr(s), dptr(d), dptr(x), dptr(y), seg.ctypes.data_as(_ip), C.byref(n_out)),
-                    "rp_lift_points")
+        self._call("points", s.size, dptr(s), dptr(d), dptr(x), dptr(y), as_ip(seg), C.byref(n_out))
         return (x, y, seg, int(n_out.value)) if want_outside else (x, y, seg)
 
     def lift(self, params: RpParams, s, s_dot, s_ddot, d, d_dot, d_ddot, lengths=None, theta0=None) -> TrajectoryLiftResult:
@@ -182,28 +107,15 @@ class TrajectoryLifter:
         [K] orientations the trajectories start with, read where one stands still from its first pose (None: ``params.x0_orientation``).
         ``params``: what ``_capi.make_params`` returns (dt, low_vel_mode, constraint_mask, x0_orientation and the vehicle limits are
         read)."""
-        s = np.atleast_2d(f64(s)) if np.ndim(s) != 2 else f64(s)
+        s, s_dot, s_ddot, d, d_dot, d_ddot = _session.six_planes("lift", s, s_dot, s_ddot, d, d_dot, d_ddot)
         K, n = s.shape
-        s_dot, s_ddot = _plane(s_dot, (K, n), "s_dot"), _plane(s_ddot, (K, n), "s_ddot")
-        d, d_dot, d_ddot = _plane(d, (K, n), "d"), _plane(d_dot, (K, n), "d_dot"), _plane(d_ddot, (K, n), "d_ddot")
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"lift: {lens.shape[0]} lengths for {K} trajectories")
-        th0 = None
-        if theta0 is not None:
-            th0 = f64(theta0).reshape(-1)
-            if th0.shape[0] != K:
-                raise ValueError(f"lift: {th0.shape[0]} orientations for {K} trajectories")
+        lens, th0 = _session.lengths_of("lift", lengths, K), _session.theta0_of("lift", theta0, K)
         out = [np.empty((K, n)) for _ in range(8)]
         status = np.empty(K, dtype=np.uint32)
         counts = np.zeros(8, dtype=np.int64)
         first, n_feasible = C.c_int64(-1), C.c_int64(0)
-        self._check(self._lib.rp_lift_evaluate(
-            self._h, C.byref(params), K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot), dptr(d_ddot),
-            lens.ctypes.data_as(_ip) if lens is not None else None, dptr(th0), 0, *[dptr(q) for q in out], status.ctypes.data_as(_up),
-            C.byref(first), C.byref(n_feasible), counts.ctypes.data_as(_lp)), "rp_lift_evaluate")
+        self._call("evaluate", C.byref(params), K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot), dptr(d_ddot), as_ip(lens), dptr(th0), 0,
+                   *[dptr(q) for q in out], status.ctypes.data_as(_up), C.byref(first), C.byref(n_feasible), counts.ctypes.data_as(_lp))
         return TrajectoryLiftResult(status, int(first.value), int(n_feasible.value), counts, *out)
 
     def lift_states(self, params: RpParams, s, s_dot, s_ddot, d, d_dot, d_ddot, lengths=None, theta0=None) -> np.ndarray:

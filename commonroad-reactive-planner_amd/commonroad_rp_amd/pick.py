@@ -13,17 +13,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpCost, RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpCost, RpParams, dptr
+from ._session import as_ip
 
 __all__ = ["TrajectoryPicker", "TrajectoryPickResult", "RpPickResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_pick.so")
+LIB_PATH = _session.lib_path("librp_pick.so")
 ABI_VERSION = 1
 TRAJ_POSES, TRAJ_SWEPT = 1, 2
 MAX_POSES = 1 << 24
@@ -54,34 +54,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_pick.so`` and declare every entry point of ``include/rp_pick.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_pick_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_pick_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -128,75 +104,20 @@ class TrajectoryPickResult:
         return (self.status >> 8) & 0xFFF
 
 
-def _plane(a, shape, name):
-    a = np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a)
-    if a.shape != shape:
-        raise ValueError(f"pick: {name} of shape {a.shape}, s of shape {shape}")
-    return a
-
-
-class TrajectoryPicker:
+class TrajectoryPicker(_session.Session):
     """Owner of one ``rp_pick`` (one HIP stream, the segment table of one reference path, obstacle tables, input and result buffers)."""
 
-    def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_pick_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_pick_last_error(self._h) if self._h else b"rp_pick_create failed"
-            self.close()
-            raise RpError(f"rp_pick_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_pick_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_pick_last_error(self._h) or b'').decode()}")
+    _prefix, _load = "rp_pick", staticmethod(load_library)
 
     def set_reference(self, ref_xy, ref_pos=None, ref_theta=None, ref_curv=None, ref_curv_d=None, d_limit: Optional[float] = None):
         """The arguments of ``TrajectoryLifter.set_reference``: the tables of ``rp_build_reference`` -- vertices [n, 2], arc lengths,
         unwrapped orientations, curvature and its derivative, [n] each -- or the package's ``CoordinateSystem`` alone (its
         projection-domain limit unless ``d_limit`` is given).  Replaces the earlier table."""
-        if ref_pos is None and hasattr(ref_xy, "ref_pos"):
-            co = ref_xy
-            ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = co.reference, co.ref_pos, co.ref_theta, co.ref_curv, co.ref_curv_d
-            if d_limit is None:
-                d_limit = co.proj_domain_d_limit
-        if ref_pos is None or ref_theta is None or ref_curv is None or ref_curv_d is None:
-            raise ValueError("set_reference: ref_xy, ref_pos, ref_theta, ref_curv and ref_curv_d, or a CoordinateSystem")
-        ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d = f64(ref_xy), f64(ref_pos), f64(ref_theta), f64(ref_curv), f64(ref_curv_d)
-        n = ref_pos.shape[0]
-        if ref_xy.shape != (n, 2) or any(q.shape != (n,) for q in (ref_pos, ref_theta, ref_curv, ref_curv_d)):
-            raise ValueError(f"set_reference: shapes {ref_xy.shape}, {ref_pos.shape}, {ref_theta.shape}, {ref_curv.shape}, {ref_curv_d.shape}, "
-                             f"not [n, 2] and four times [n]")
-        self._check(self._lib.rp_pick_set_reference(self._h, n, dptr(ref_xy), dptr(ref_pos), dptr(ref_theta), dptr(ref_curv), dptr(ref_curv_d),
-                                                    20.0 if d_limit is None else float(d_limit)), "rp_pick_set_reference")
+        self._set_reference(ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, d_limit)
 
     def set_obstacles(self, tables=None):
         """The tables ``RpContext.set_obstacles`` takes (``ObstacleTables``; None: empty); they replace the earlier ones."""
-        from .collision import ObstacleTables
-        tb = tables if tables is not None else ObstacleTables()
-        nd, ns = tb.dyn_obb.shape[0], tb.dyn_obb.shape[1]
-        self._check(self._lib.rp_pick_set_obstacles(
-            self._h, len(tb.static_obb), dptr(tb.static_obb), len(tb.static_tri), dptr(tb.static_tri),
-            len(tb.static_circ), dptr(tb.static_circ), nd, ns, int(tb.dyn_t0), dptr(tb.dyn_obb)), "rp_pick_set_obstacles")
+        self._set_obstacles(tables)
 
     def pick(self, params: RpParams, cost: RpCost, s, s_dot, s_ddot, d, d_dot, d_ddot, lengths=None, theta0=None, poses: bool = True,
              swept: bool = False, want_planes: bool = False, want_hits: bool = False) -> TrajectoryPickResult:
@@ -205,20 +126,9 @@ class TrajectoryPicker:
         index ``time_step0 + i * factor``; ``swept``: the continuous test of segment i at ``time_step0 + i``; neither: no collision test.
         ``want_planes``: the eight pose planes come back (otherwise none of them leaves the device); ``want_hits``: the first-hit arrays
         of the requested tests come back.  ``params``, ``cost``: what ``_capi.make_params`` and ``_capi.make_cost`` return."""
-        s = np.atleast_2d(f64(s)) if np.ndim(s) != 2 else f64(s)
+        s, s_dot, s_ddot, d, d_dot, d_ddot = _session.six_planes("pick", s, s_dot, s_ddot, d, d_dot, d_ddot)
         K, n = s.shape
-        s_dot, s_ddot = _plane(s_dot, (K, n), "s_dot"), _plane(s_ddot, (K, n), "s_ddot")
-        d, d_dot, d_ddot = _plane(d, (K, n), "d"), _plane(d_dot, (K, n), "d_dot"), _plane(d_ddot, (K, n), "d_ddot")
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"pick: {lens.shape[0]} lengths for {K} trajectories")
-        th0 = None
-        if theta0 is not None:
-            th0 = f64(theta0).reshape(-1)
-            if th0.shape[0] != K:
-                raise ValueError(f"pick: {th0.shape[0]} orientations for {K} trajectories")
+        lens, th0 = _session.lengths_of("pick", lengths, K), _session.theta0_of("pick", theta0, K)
         mode = (TRAJ_POSES if poses else 0) | (TRAJ_SWEPT if swept else 0)
         planes = [np.empty((K, n)) if want_planes else None for _ in PLANES]
         status, costs = np.empty(K, dtype=np.uint32), np.empty(K)
@@ -226,11 +136,9 @@ class TrajectoryPicker:
         first_seg = np.empty(K, dtype=np.int32) if want_hits and swept else None
         res = RpPickResult()
         block = np.empty((RP_N_ARRAYS, n))
-        as_ip = lambda a: a.ctypes.data_as(_ip) if a is not None else None   # noqa: E731
-        self._check(self._lib.rp_pick_select(
-            self._h, C.byref(params), C.byref(cost), mode, K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot), dptr(d_ddot),
-            as_ip(lens), dptr(th0), 0, *[dptr(q) for q in planes], status.ctypes.data_as(_up), dptr(costs), as_ip(first_pose), as_ip(first_seg),
-            C.byref(res), dptr(block)), "rp_pick_select")
+        self._call("select", C.byref(params), C.byref(cost), mode, K, n, dptr(s), dptr(s_dot), dptr(s_ddot), dptr(d), dptr(d_dot), dptr(d_ddot),
+                   as_ip(lens), dptr(th0), 0, *[dptr(q) for q in planes], status.ctypes.data_as(_up), dptr(costs), as_ip(first_pose), as_ip(first_seg),
+                   C.byref(res), dptr(block))
         return TrajectoryPickResult(status, costs, int(res.best), float(res.best_cost), block if res.best >= 0 else None, int(res.n_feasible),
                                     int(res.n_collision), int(res.n_collision_before_best), np.array(res.reason_counts[:], dtype=np.int64),
                                     *planes, first_pose, first_seg)

@@ -12,17 +12,17 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import os
-import sys
 from typing import Optional
 
 import numpy as np
 
-from ._capi import RpCost, RpError, RpLibraryMissing, RpParams, dptr, f64
+from . import _session
+from ._capi import RpCost, RpParams, dptr, f64
+from ._session import as_ip
 
 __all__ = ["TrajectoryScorer", "TrajectoryScoreResult", "load_library", "EXPORTED_SYMBOLS", "LIB_PATH"]
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librp_score.so")
+LIB_PATH = _session.lib_path("librp_score.so")
 ABI_VERSION = 1
 MAX_POSES = 1 << 24
 EXHAUSTIVE = 1   # RP_SCORE_EXHAUSTIVE: walk every segment, no pruning (a diagnostic; results do not depend on it)
@@ -41,34 +41,10 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_lib = None
-
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """Load ``librp_score.so`` and declare every entry point of ``include/rp_score.h``."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    # one HIP runtime per process, torch's when it is installed (see _capi.load_library, same switch)
-    if "torch" not in sys.modules and not os.environ.get("RP_AMD_NO_TORCH_PRELOAD"):
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-    if not os.path.exists(path):
-        raise RpLibraryMissing(
-            f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
-            f"or make -C commonroad-reactive-planner_amd/csrc). There is no CPU fallback.")
-    lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    if lib.rp_score_abi_version() != ABI_VERSION:
-        raise RpError(f"{path}: ABI version {lib.rp_score_abi_version()}, this binding speaks {ABI_VERSION}")
-    if path == LIB_PATH:
-        _lib = lib
-    return lib
+    return _session.load_library(path, LIB_PATH, _SIGNATURES, ABI_VERSION)
 
 
 @dataclasses.dataclass
@@ -101,49 +77,10 @@ class TrajectoryScoreResult:
         return (self.status >> 8) & 0xFFF
 
 
-def _plane(a, shape, name):
-    if a is None:
-        return None
-    a = np.atleast_2d(f64(a)) if np.ndim(a) != 2 else f64(a)
-    if a.shape != shape:
-        raise ValueError(f"score: {name} of shape {a.shape}, x of shape {shape}")
-    return a
-
-
-class TrajectoryScorer:
+class TrajectoryScorer(_session.Session):
     """Owner of one ``rp_score`` (one HIP stream, the segment table of one reference path, pose and result buffers)."""
 
-    def __init__(self, device: int = 0, library: Optional[str] = None):
-        self._lib = load_library(library)
-        self._h = C.c_void_p()
-        rc = self._lib.rp_score_create(C.byref(self._h), int(device))
-        if rc != 0:
-            msg = self._lib.rp_score_last_error(self._h) if self._h else b"rp_score_create failed"
-            self.close()
-            raise RpError(f"rp_score_create(device={device}) -> {rc}: {(msg or b'').decode()}")
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rp_score_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            raise RpError(f"{what} -> {rc}: {(self._lib.rp_score_last_error(self._h) or b'').decode()}")
+    _prefix, _load = "rp_score", staticmethod(load_library)
 
     def set_reference(self, ref_xy, ref_pos=None, ref_theta=None, d_limit: Optional[float] = None):
         """The tables ``RpContext.set_reference`` takes: vertices [n, 2], arc lengths [n], unwrapped orientations [n]; or the
@@ -159,8 +96,7 @@ class TrajectoryScorer:
         n = ref_pos.shape[0]
         if ref_xy.shape != (n, 2) or ref_pos.shape != (n,) or ref_theta.shape != (n,):
             raise ValueError(f"set_reference: shapes {ref_xy.shape}, {ref_pos.shape}, {ref_theta.shape}, not [n, 2], [n], [n]")
-        self._check(self._lib.rp_score_set_reference(self._h, n, dptr(ref_xy), dptr(ref_pos), dptr(ref_theta),
-                                                     20.0 if d_limit is None else float(d_limit)), "rp_score_set_reference")
+        self._call("set_reference", n, dptr(ref_xy), dptr(ref_pos), dptr(ref_theta), 20.0 if d_limit is None else float(d_limit))
 
     def project(self, x, y, want_outside: bool = False):
         """(s, d, segment) of a batch of points, in the shape of ``x``: NaN, NaN, -1 outside the projection domain.  With
@@ -170,8 +106,7 @@ class TrajectoryScorer:
             raise ValueError(f"project: x of shape {x.shape}, y of shape {y.shape}")
         s, d, seg = np.empty(x.shape), np.empty(x.shape), np.empty(x.shape, dtype=np.int32)
         n_out = C.c_int64(0)
-        self._check(self._lib.rp_score_project(self._h, x.size, dptr(x), dptr(y), dptr(s), dptr(d), seg.ctypes.data_as(_ip), C.byref(n_out)),
-                    "rp_score_project")
+        self._call("project", x.size, dptr(x), dptr(y), dptr(s), dptr(d), as_ip(seg), C.byref(n_out))
         return (s, d, seg, int(n_out.value)) if want_outside else (s, d, seg)
 
     def score(self, params: RpParams, cost: RpCost, x, y, theta, v=None, a=None, kappa=None, lengths=None, want_states: bool = False,
@@ -179,23 +114,17 @@ class TrajectoryScorer:
         """``x``, ``y``, ``theta`` (and ``v``, ``a``, ``kappa`` where a check or a cost term reads them): [K, n] (one trajectory may
         come as 1-D); ``lengths``: [K] valid poses per trajectory (None: n).  ``params``: what ``_capi.make_params`` returns (dt,
         constraint_mask and the vehicle limits are read), ``cost``: what ``_capi.make_cost`` returns."""
-        x = np.atleast_2d(f64(x)) if np.ndim(x) != 2 else f64(x)
+        x = _session.plane(x, None, "score", "x", "x")
         K, n = x.shape
-        y, theta = _plane(y, (K, n), "y"), _plane(theta, (K, n), "theta")
-        v, a, kappa = _plane(v, (K, n), "v"), _plane(a, (K, n), "a"), _plane(kappa, (K, n), "kappa")
-        lens = None
-        if lengths is not None:
-            lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
-            if lens.shape[0] != K:
-                raise ValueError(f"score: {lens.shape[0]} lengths for {K} trajectories")
+        y, theta, v, a, kappa = (_session.plane(q, (K, n), "score", name, "x") for q, name in ((y, "y"), (theta, "theta"), (v, "v"), (a, "a"), (kappa, "kappa")))
+        lens = _session.lengths_of("score", lengths, K)
         s, d, tcl = (np.empty((K, n)), np.empty((K, n)), np.empty((K, n))) if want_states else (None, None, None)
         status, cst = np.empty(K, dtype=np.uint32), np.empty(K, dtype=np.float64)
         counts = np.zeros(8, dtype=np.int64)
         best, best_cost, n_feasible = C.c_int64(-1), C.c_double(float("nan")), C.c_int64(0)
-        self._check(self._lib.rp_score_evaluate(
-            self._h, C.byref(params), C.byref(cost), K, n, dptr(x), dptr(y), dptr(theta), dptr(v), dptr(a), dptr(kappa),
-            lens.ctypes.data_as(_ip) if lens is not None else None, int(flags), dptr(s), dptr(d), dptr(tcl), status.ctypes.data_as(_up), dptr(cst),
-            C.byref(best), C.byref(best_cost), C.byref(n_feasible), counts.ctypes.data_as(_lp)), "rp_score_evaluate")
+        self._call("evaluate", C.byref(params), C.byref(cost), K, n, dptr(x), dptr(y), dptr(theta), dptr(v), dptr(a), dptr(kappa), as_ip(lens), int(flags),
+                   dptr(s), dptr(d), dptr(tcl), status.ctypes.data_as(_up), dptr(cst), C.byref(best), C.byref(best_cost), C.byref(n_feasible),
+                   counts.ctypes.data_as(_lp))
         return TrajectoryScoreResult(status, cst, int(best.value), float(best_cost.value), int(n_feasible.value), counts, s, d, tcl)
 
     def score_states(self, params: RpParams, cost: RpCost, states, lengths=None, **kw) -> TrajectoryScoreResult:

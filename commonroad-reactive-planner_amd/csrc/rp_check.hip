@@ -12,7 +12,8 @@
 #include <string>
 #include <vector>
 
-#include "rp_check_rules.h"   // the tables' layout and builder, cc.collide and both tests of a chunk: shared with rp_pick.hip
+#include "rp_check_rules.h"   // the tables as the kernels see them, cc.collide and both tests of a chunk: shared with rp_pick.hip
+#include "rp_session.h"       // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_check.h"
 
 namespace {
@@ -79,86 +80,20 @@ __global__ __launch_bounds__(CK_BLOCK) void rp_check_reduce_kernel(int K, int32_
 
 }  // namespace
 
-struct rp_checker {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_checker : RpSession {
     CkTables tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-    double *d_stat = nullptr, *d_dyn = nullptr;
-    // poses (and lengths) of a call: pinned host block and its device copy; results likewise.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_in = 0, cap_out = 0;
+    RpTable d_stat, d_dyn;
 };
-
-namespace {
-
-int fail(rp_checker *ck, int code, const std::string &msg) {
-    ck->err = msg;
-    return code;
-}
-
-#define CK_TRY(ck, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ck, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int upload(rp_checker *ck, double *&dst, const std::vector<double> &src) {
-    if (dst) { CK_TRY(ck, hipFree(dst)); dst = nullptr; }
-    if (src.empty()) return RP_OK;
-    CK_TRY(ck, hipMalloc((void **)&dst, src.size() * sizeof(double)));
-    CK_TRY(ck, hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
-    return RP_OK;
-}
-
-int grow_pair(rp_checker *ck, void *&host, void *&dev, size_t &cap, size_t need) {
-    if (need <= cap) return RP_OK;
-    if (host) { CK_TRY(ck, hipHostFree(host)); host = nullptr; }
-    if (dev) { CK_TRY(ck, hipFree(dev)); dev = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if (hipHostMalloc(&host, want, hipHostMallocDefault) != hipSuccess) { host = nullptr; return fail(ck, RP_ENOMEM, "rp_checker_check: pinned host memory"); }
-    if (hipMalloc(&dev, want) != hipSuccess) { dev = nullptr; return fail(ck, RP_ENOMEM, "rp_checker_check: device memory"); }
-    cap = want;
-    return RP_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
 int rp_checker_abi_version(void) { return RP_CHECKER_ABI_VERSION; }
 
-int rp_checker_create(rp_checker **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_checker *ck = new (std::nothrow) rp_checker();
-    if (!ck) return RP_ENOMEM;
-    *out = ck;   // returned even on failure so that rp_checker_last_error works; the caller destroys it
-    ck->device = device;
-    int ndev = 0;
-    CK_TRY(ck, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ck, RP_EINVAL, "no such HIP device");
-    CK_TRY(ck, hipSetDevice(device));
-    CK_TRY(ck, hipStreamCreateWithFlags(&ck->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_checker_create(rp_checker **out, int device) { return session_create(out, device); }
 
-void rp_checker_destroy(rp_checker *ck) {
-    if (!ck) return;
-    (void)hipSetDevice(ck->device);
-    if (ck->stream) (void)hipStreamSynchronize(ck->stream);
-    void *dev[] = {ck->d_stat, ck->d_dyn, ck->d_in, ck->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (ck->h_in) (void)hipHostFree(ck->h_in);
-    if (ck->h_out) (void)hipHostFree(ck->h_out);
-    if (ck->stream) (void)hipStreamDestroy(ck->stream);
-    delete ck;
-}
+void rp_checker_destroy(rp_checker *ck) { session_destroy(ck); }
 
-const char *rp_checker_last_error(const rp_checker *ck) { return ck ? ck->err.c_str() : "null checker"; }
+const char *rp_checker_last_error(const rp_checker *ck) { return session_last_error(ck, "null checker"); }
 
 int rp_checker_set_obstacles(rp_checker *ck, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ,
                              const double *circ, int32_t n_dyn, int32_t n_steps, int32_t dyn_t0, const double *dyn) {
@@ -166,16 +101,11 @@ int rp_checker_set_obstacles(rp_checker *ck, int32_t n_sobb, const double *sobb,
     if (!ck->stream) return fail(ck, RP_ESTATE, "rp_checker_set_obstacles: the checker has no device (rp_checker_create failed)");
     std::vector<double> a, e;
     std::string msg;
-    const int built = ck_build_tables("rp_checker_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
-    if (built != RP_OK) return fail(ck, built, msg);
-    CK_TRY(ck, hipSetDevice(ck->device));
-    CK_TRY(ck, hipStreamSynchronize(ck->stream));
-    const size_t plane = (size_t)n_dyn * (size_t)n_steps;
-    ck->tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};   // (a failed upload leaves empty tables, never half of the new ones)
-    int rc;
-    if ((rc = upload(ck, ck->d_stat, a)) != RP_OK) return rc;
-    if ((rc = upload(ck, ck->d_dyn, e)) != RP_OK) return rc;
-    ck->tb = {ck->d_stat, ck->d_dyn, n_sobb, n_tri, n_circ, plane ? n_dyn : 0, plane ? n_steps : 0, dyn_t0};
+    int rc = ot_build("rp_checker_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
+    if (rc != RP_OK) return fail(ck, rc, msg);
+    if ((rc = replace_tables(ck, {{&ck->d_stat, &a}, {&ck->d_dyn, &e}})) != RP_OK) return rc;
+    const bool any_dyn = !e.empty();
+    ck->tb = {ck->d_stat.p, ck->d_dyn.p, n_sobb, n_tri, n_circ, any_dyn ? n_dyn : 0, any_dyn ? n_steps : 0, dyn_t0};
     return RP_OK;
 }
 
@@ -201,26 +131,25 @@ int rp_checker_check(rp_checker *ck, const rp_params *p, uint32_t mode, int64_t 
         return RP_OK;
     }
     if (!ck->stream) return fail(ck, RP_ESTATE, "rp_checker_check: the checker has no device (rp_checker_create failed)");
-    CK_TRY(ck, hipSetDevice(ck->device));
+    RP_TRY(ck, hipSetDevice(ck->device));
     const size_t P = (size_t)K * (size_t)n_poses;
     const size_t in_bytes = 3 * P * sizeof(double) + (len ? (size_t)K * sizeof(int32_t) : 0);
     const size_t first_off = 2 * sizeof(unsigned long long), hits_off = first_off + 2 * (size_t)K * sizeof(int32_t);
     const size_t out_bytes = hits_off + (pose_hit ? P : 0);
-    int rc;
-    if ((rc = grow_pair(ck, ck->h_in, ck->d_in, ck->cap_in, in_bytes)) != RP_OK) return rc;
-    if ((rc = grow_pair(ck, ck->h_out, ck->d_out, ck->cap_out, out_bytes)) != RP_OK) return rc;
-    double *h_poses = static_cast<double *>(ck->h_in);
+    const int rc = grow_call(ck, "rp_checker_check", in_bytes, out_bytes, out_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_poses = static_cast<double *>(ck->h_in.p);
     std::memcpy(h_poses, x, P * sizeof(double));
     std::memcpy(h_poses + P, y, P * sizeof(double));
     std::memcpy(h_poses + 2 * P, theta, P * sizeof(double));
     if (len) std::memcpy(h_poses + 3 * P, len, (size_t)K * sizeof(int32_t));
-    CK_TRY(ck, hipMemcpyAsync(ck->d_in, ck->h_in, in_bytes, hipMemcpyHostToDevice, ck->stream));
-    char *d_out = static_cast<char *>(ck->d_out);
+    RP_TRY(ck, hipMemcpyAsync(ck->d_in.p, ck->h_in.p, in_bytes, hipMemcpyHostToDevice, ck->stream));
+    char *d_out = static_cast<char *>(ck->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(d_out);
     int32_t *d_first_pose = reinterpret_cast<int32_t *>(d_out + first_off), *d_first_seg = d_first_pose + K;
     uint8_t *d_hits = pose_hit ? reinterpret_cast<uint8_t *>(d_out + hits_off) : nullptr;
-    CK_TRY(ck, hipMemsetAsync(d_first_pose, 0x7f, 2 * (size_t)K * sizeof(int32_t), ck->stream));
-    const double *d_poses = static_cast<const double *>(ck->d_in);
+    RP_TRY(ck, hipMemsetAsync(d_first_pose, 0x7f, 2 * (size_t)K * sizeof(int32_t), ck->stream));
+    const double *d_poses = static_cast<const double *>(ck->d_in.p);
     const int32_t *d_len = len ? reinterpret_cast<const int32_t *>(d_poses + 3 * P) : nullptr;
     const int nchunk = (n_poses + 63) / 64;
     const long long waves = (long long)K * nchunk;
@@ -230,13 +159,13 @@ int rp_checker_check(rp_checker *ck, const rp_params *p, uint32_t mode, int64_t 
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(CK_BLOCK), 0, ck->stream, ck->tb, d_poses, d_len, (int)K, (int)n_poses, nchunk, mode,
                        p->wb_rear_axle, 0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor, d_first_pose, d_first_seg, d_hits,
                        d_red);
-    CK_TRY(ck, hipGetLastError());
+    RP_TRY(ck, hipGetLastError());
     hipLaunchKernelGGL(rp_check_reduce_kernel, dim3((unsigned)((K + CK_BLOCK - 1) / CK_BLOCK)), dim3(CK_BLOCK), 0, ck->stream, (int)K, d_first_pose,
                        d_first_seg, d_red);
-    CK_TRY(ck, hipGetLastError());
-    CK_TRY(ck, hipMemcpyAsync(ck->h_out, ck->d_out, out_bytes, hipMemcpyDeviceToHost, ck->stream));
-    CK_TRY(ck, hipStreamSynchronize(ck->stream));
-    const char *h_out = static_cast<const char *>(ck->h_out);
+    RP_TRY(ck, hipGetLastError());
+    RP_TRY(ck, hipMemcpyAsync(ck->h_out.p, ck->d_out.p, out_bytes, hipMemcpyDeviceToHost, ck->stream));
+    RP_TRY(ck, hipStreamSynchronize(ck->stream));
+    const char *h_out = static_cast<const char *>(ck->h_out.p);
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (first_free) *first_free = h_red[0] < (unsigned long long)K ? (int64_t)h_red[0] : -1;
     if (n_hit) *n_hit = (int64_t)h_red[1];

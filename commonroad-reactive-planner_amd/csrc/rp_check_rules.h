@@ -1,6 +1,6 @@
-// rp_check_rules.h -- the obstacle walk of include/rp_check.h, stated once: the layout of the obstacle tables and their builder,
-// cc.collide of one rectangle against them, and both tests of one 64-pose chunk of a trajectory.  Included by rp_check.hip
-// (librp_check.so) and by rp_pick.hip (librp_pick.so); everything here has internal linkage, nothing of it is exported by either.
+// rp_check_rules.h -- the obstacle walk of include/rp_check.h, stated once: the obstacle tables as the kernels see them, cc.collide
+// of one rectangle against them, and both tests of one 64-pose chunk of a trajectory.  The tables' host builder is
+// rp_obstacle_tables.h, included here.  Everything here has internal linkage, nothing of it is exported by a library that includes it.
 #ifndef RP_CHECK_RULES_H
 #define RP_CHECK_RULES_H
 
@@ -12,18 +12,16 @@
 #include <vector>
 
 #include "rp_device.h"
+#include "rp_obstacle_tables.h"
 #include "../../include/rp_check.h"
 
 namespace {
 
-constexpr int CK_ROW = 10;                      // doubles per static row (below)
+constexpr int CK_ROW = OT_ROW;                  // doubles per static row (rp_obstacle_tables.h)
 constexpr int32_t CK_NONE = 0x7f7f7f7f;         // "no hit yet" of the first-hit arrays (a byte fill), above every pose index
 
-// Static shapes as ONE table, rectangles first, then triangles, then circles; every lane of a wavefront reads the same row
-// (a broadcast from LDS, or a scalar load).  Row: [0..5] the shape -- rectangle cx, cy, ux, uy, hl, hw | triangle x1 .. y3 |
-// circle cx, cy, r -- then [6..8] its bounding circle cx, cy, r and one double of padding.
-// Dynamic rectangles: struct-of-arrays planes [7][n_dyn][n_steps] cx, cy, ux, uy, hl, hw, r_bound (cx = NaN: absent), so that the
-// lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
+// The tables of rp_obstacle_tables.h.  Every lane of a wavefront reads the same static row (a broadcast from LDS, or a scalar load);
+// the dynamic planes are laid out so that the lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
 struct CkTables {
     const double *stat;
     const double *dyn;
@@ -104,54 +102,6 @@ __device__ __forceinline__ bool ck_segment_hit(const CkTables &tb, const double 
     }
     const Obb m = merge_swept(ego, seg ? nxt : ego);
     return ck_collides<LDS>(tb, lds_rows, m, sqrt(m.hl * m.hl + m.hw * m.hw), (long long)t0 + (long long)i, seg);
-}
-
-// ---- host: rp_checker_set_obstacles' refusals and its two tables -----------------------------------------------------------------
-// RP_OK, the static rows `a` and the dynamic planes `e`, or the code (RP_EINVAL, RP_ENOMEM) and the message behind `who: `.
-inline int ck_build_tables(const char *who, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ, const double *circ,
-                           int32_t n_dyn, int32_t n_steps, const double *dyn, std::vector<double> &a, std::vector<double> &e, std::string &msg) {
-    const std::string w = std::string(who) + ": ";
-    if (n_sobb < 0 || n_tri < 0 || n_circ < 0 || n_dyn < 0 || n_steps < 0 || (n_sobb && !sobb) || (n_tri && !tri) || (n_circ && !circ) ||
-        (n_dyn && n_steps && !dyn)) {
-        msg = w + "negative count or null table";
-        return RP_EINVAL;
-    }
-    if ((int64_t)n_sobb + n_tri + n_circ > INT32_MAX / CK_ROW) { msg = w + "too many static shapes"; return RP_EINVAL; }
-    try {
-        a.assign(((size_t)n_sobb + (size_t)n_tri + (size_t)n_circ) * CK_ROW, 0.0);
-        e.assign((size_t)7 * (size_t)n_dyn * (size_t)n_steps, 0.0);
-    } catch (const std::bad_alloc &) {
-        msg = w + "host memory";
-        return RP_ENOMEM;
-    }
-    double *r = a.data();
-    for (int j = 0; j < n_sobb; ++j, r += CK_ROW) {   // (ux, uy from the host's cos / sin, as rp_set_obstacles)
-        const double *o = sobb + 5 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = std::cos(o[2]); r[3] = std::sin(o[2]); r[4] = o[3]; r[5] = o[4];
-        r[6] = o[0]; r[7] = o[1]; r[8] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    for (int j = 0; j < n_tri; ++j, r += CK_ROW) {
-        const double *o = tri + 6 * (size_t)j;
-        for (int q = 0; q < 6; ++q) r[q] = o[q];
-        const double bx = (o[0] + o[2] + o[4]) / 3.0, by = (o[1] + o[3] + o[5]) / 3.0;
-        double rr = 0.0;
-        for (int q = 0; q < 3; ++q) rr = std::fmax(rr, std::hypot(o[2 * q] - bx, o[2 * q + 1] - by));
-        r[6] = bx; r[7] = by; r[8] = rr;
-    }
-    for (int j = 0; j < n_circ; ++j, r += CK_ROW) {
-        const double *o = circ + 3 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
-        r[6] = o[0]; r[7] = o[1]; r[8] = o[2];
-    }
-    const size_t plane = (size_t)n_dyn * (size_t)n_steps;
-    for (size_t at = 0; at < plane; ++at) {
-        const double *o = dyn + 5 * at;
-        e[at] = o[0]; e[plane + at] = o[1];
-        e[2 * plane + at] = std::cos(o[2]); e[3 * plane + at] = std::sin(o[2]);
-        e[4 * plane + at] = o[3]; e[5 * plane + at] = o[4];
-        e[6 * plane + at] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    return RP_OK;
 }
 
 }  // namespace

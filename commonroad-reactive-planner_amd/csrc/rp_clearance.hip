@@ -14,21 +14,21 @@
 #include <vector>
 
 #include "rp_device.h"
+#include "rp_obstacle_tables.h"   // the tables' layout and host builder: shared with the checkers and the picks
+#include "rp_session.h"           // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_clearance.h"
 
 namespace {
 
 constexpr int CL_BLOCK = 256;                   // four wavefronts per workgroup
 constexpr int CL_WAVES = CL_BLOCK / 64;
-constexpr int CL_ROW = 10;                      // doubles per static row (below)
+constexpr int CL_ROW = OT_ROW;                  // doubles per static row (rp_obstacle_tables.h)
 constexpr int CL_LDS_ROWS = 128;                // static rows staged in LDS (10 KiB per workgroup); more: read from device memory
 constexpr int CL_FINAL_BLOCK = 1024;            // the one workgroup of rp_clearance_final_kernel
 constexpr double CL_TINY = RP_CLEARANCE_TINY;
 
-// Static shapes as ONE table in id order, rectangles first, then triangles, then circles; every lane of a wavefront reads the same
-// row (a broadcast from LDS, or a scalar load).  Row: [0..5] the shape -- rectangle cx, cy, ux, uy, hl, hw | triangle x1 .. y3 |
-// circle cx, cy, r -- then [6..8] its bounding circle cx, cy, r and one double of padding.
-// Dynamic rectangles: struct-of-arrays planes [7][n_dyn][n_steps] cx, cy, ux, uy, hl, hw, r_bound (cx = NaN: absent), so that the
+// The tables of rp_obstacle_tables.h; the order of the static rows and then of the dynamic obstacles is the order of the ids.  Every
+// lane of a wavefront reads the same static row (a broadcast from LDS, or a scalar load); the dynamic planes are laid out so that the
 // lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
 struct ClTables {
     const double *stat;
@@ -269,139 +269,35 @@ __global__ __launch_bounds__(CL_FINAL_BLOCK) void rp_clearance_final_kernel(long
 
 }  // namespace
 
-struct rp_clearance {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_clearance : RpSession {
     ClTables tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-    double *d_stat = nullptr, *d_dyn = nullptr;
-    // poses (and lengths) of a call: pinned host block and its device copy; the results on the device (per pose, per trajectory, the
-    // scalars) and a pinned host block for the part of them a call asks for.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_stat, d_dyn;
 };
-
-namespace {
-
-int fail(rp_clearance *cl, int code, const std::string &msg) {
-    cl->err = msg;
-    return code;
-}
-
-#define CL_TRY(cl, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(cl, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int upload(rp_clearance *cl, double *&dst, const std::vector<double> &src) {
-    if (dst) { CL_TRY(cl, hipFree(dst)); dst = nullptr; }
-    if (src.empty()) return RP_OK;
-    CL_TRY(cl, hipMalloc((void **)&dst, src.size() * sizeof(double)));
-    CL_TRY(cl, hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
-    return RP_OK;
-}
-
-int grow(rp_clearance *cl, void *&buf, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (buf) { CL_TRY(cl, pinned ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&buf, want, hipHostMallocDefault) : hipMalloc(&buf, want)) != hipSuccess) {
-        buf = nullptr;
-        return fail(cl, RP_ENOMEM, pinned ? "rp_clearance_query: pinned host memory" : "rp_clearance_query: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
 int rp_clearance_abi_version(void) { return RP_CLEARANCE_ABI_VERSION; }
 
-int rp_clearance_create(rp_clearance **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_clearance *cl = new (std::nothrow) rp_clearance();
-    if (!cl) return RP_ENOMEM;
-    *out = cl;   // returned even on failure so that rp_clearance_last_error works; the caller destroys it
-    cl->device = device;
-    int ndev = 0;
-    CL_TRY(cl, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(cl, RP_EINVAL, "no such HIP device");
-    CL_TRY(cl, hipSetDevice(device));
-    CL_TRY(cl, hipStreamCreateWithFlags(&cl->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_clearance_create(rp_clearance **out, int device) { return session_create(out, device); }
 
-void rp_clearance_destroy(rp_clearance *cl) {
-    if (!cl) return;
-    (void)hipSetDevice(cl->device);
-    if (cl->stream) (void)hipStreamSynchronize(cl->stream);
-    void *dev[] = {cl->d_stat, cl->d_dyn, cl->d_in, cl->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (cl->h_in) (void)hipHostFree(cl->h_in);
-    if (cl->h_out) (void)hipHostFree(cl->h_out);
-    if (cl->stream) (void)hipStreamDestroy(cl->stream);
-    delete cl;
-}
+void rp_clearance_destroy(rp_clearance *cl) { session_destroy(cl); }
 
-const char *rp_clearance_last_error(const rp_clearance *cl) { return cl ? cl->err.c_str() : "null clearance object"; }
+const char *rp_clearance_last_error(const rp_clearance *cl) { return session_last_error(cl, "null clearance object"); }
 
 int rp_clearance_set_obstacles(rp_clearance *cl, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ,
                                const double *circ, int32_t n_dyn, int32_t n_steps, int32_t dyn_t0, const double *dyn) {
     if (!cl) return RP_EINVAL;
     if (!cl->stream) return fail(cl, RP_ESTATE, "rp_clearance_set_obstacles: the object has no device (rp_clearance_create failed)");
-    if (n_sobb < 0 || n_tri < 0 || n_circ < 0 || n_dyn < 0 || n_steps < 0 || (n_sobb && !sobb) || (n_tri && !tri) || (n_circ && !circ) ||
-        (n_dyn && n_steps && !dyn))
-        return fail(cl, RP_EINVAL, "rp_clearance_set_obstacles: negative count or null table");
-    if ((int64_t)n_sobb + n_tri + n_circ > INT32_MAX / CL_ROW) return fail(cl, RP_EINVAL, "rp_clearance_set_obstacles: too many static shapes");
-    if ((int64_t)n_sobb + n_tri + n_circ + n_dyn > INT32_MAX) return fail(cl, RP_EINVAL, "rp_clearance_set_obstacles: too many obstacles for an int32 id");
-    CL_TRY(cl, hipSetDevice(cl->device));
-    CL_TRY(cl, hipStreamSynchronize(cl->stream));
     std::vector<double> a, e;
-    try {
-        a.assign(((size_t)n_sobb + (size_t)n_tri + (size_t)n_circ) * CL_ROW, 0.0);
-        e.assign((size_t)7 * (size_t)n_dyn * (size_t)n_steps, 0.0);
-    } catch (const std::bad_alloc &) {
-        return fail(cl, RP_ENOMEM, "rp_clearance_set_obstacles: host memory");
-    }
-    double *r = a.data();
-    for (int j = 0; j < n_sobb; ++j, r += CL_ROW) {   // (ux, uy from the host's cos / sin, as rp_checker_set_obstacles)
-        const double *o = sobb + 5 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = std::cos(o[2]); r[3] = std::sin(o[2]); r[4] = o[3]; r[5] = o[4];
-        r[6] = o[0]; r[7] = o[1]; r[8] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    for (int j = 0; j < n_tri; ++j, r += CL_ROW) {
-        const double *o = tri + 6 * (size_t)j;
-        for (int q = 0; q < 6; ++q) r[q] = o[q];
-        const double bx = (o[0] + o[2] + o[4]) / 3.0, by = (o[1] + o[3] + o[5]) / 3.0;
-        double rr = 0.0;
-        for (int q = 0; q < 3; ++q) rr = std::fmax(rr, std::hypot(o[2 * q] - bx, o[2 * q + 1] - by));
-        r[6] = bx; r[7] = by; r[8] = rr;
-    }
-    for (int j = 0; j < n_circ; ++j, r += CL_ROW) {
-        const double *o = circ + 3 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
-        r[6] = o[0]; r[7] = o[1]; r[8] = o[2];
-    }
-    const size_t plane = (size_t)n_dyn * (size_t)n_steps;
-    for (size_t at = 0; at < plane; ++at) {
-        const double *o = dyn + 5 * at;
-        e[at] = o[0]; e[plane + at] = o[1];
-        e[2 * plane + at] = std::cos(o[2]); e[3 * plane + at] = std::sin(o[2]);
-        e[4 * plane + at] = o[3]; e[5 * plane + at] = o[4];
-        e[6 * plane + at] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    cl->tb = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};   // (a failed upload leaves empty tables, never half of the new ones)
-    int rc;
-    if ((rc = upload(cl, cl->d_stat, a)) != RP_OK) return rc;
-    if ((rc = upload(cl, cl->d_dyn, e)) != RP_OK) return rc;
-    cl->tb = {cl->d_stat, cl->d_dyn, n_sobb, n_tri, n_circ, plane ? n_dyn : 0, plane ? n_steps : 0, dyn_t0};
+    std::string msg;
+    int rc = ot_refuse("rp_clearance_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, msg);
+    if (rc != RP_OK) return fail(cl, rc, msg);
+    if ((int64_t)n_sobb + n_tri + n_circ + n_dyn > INT32_MAX) return fail(cl, RP_EINVAL, "rp_clearance_set_obstacles: too many obstacles for an int32 id");
+    rc = ot_fill("rp_clearance_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
+    if (rc != RP_OK) return fail(cl, rc, msg);
+    if ((rc = replace_tables(cl, {{&cl->d_stat, &a}, {&cl->d_dyn, &e}})) != RP_OK) return rc;
+    const bool any_dyn = !e.empty();
+    cl->tb = {cl->d_stat.p, cl->d_dyn.p, n_sobb, n_tri, n_circ, any_dyn ? n_dyn : 0, any_dyn ? n_steps : 0, dyn_t0};
     return RP_OK;
 }
 
@@ -427,7 +323,7 @@ int rp_clearance_query(rp_clearance *cl, const rp_params *p, int64_t K, int32_t 
         return RP_OK;
     }
     if (!cl->stream) return fail(cl, RP_ESTATE, "rp_clearance_query: the object has no device (rp_clearance_create failed)");
-    CL_TRY(cl, hipSetDevice(cl->device));
+    RP_TRY(cl, hipSetDevice(cl->device));
     const size_t P = (size_t)K * (size_t)n_poses, Kz = (size_t)K;
     const size_t in_bytes = 3 * P * sizeof(double) + (len ? Kz * sizeof(int32_t) : 0);
     // results on the device: scalars | min_clearance [K] | min_pose [K] | nearest [K] | (8-byte aligned) pose clearance [P] | pose id [P];
@@ -436,23 +332,20 @@ int rp_clearance_query(rp_clearance *cl, const rp_params *p, int64_t K, int32_t 
     const size_t pc_off = (near_off + Kz * sizeof(int32_t) + 7) & ~(size_t)7, id_off = pc_off + P * sizeof(double);
     const size_t dev_bytes = id_off + P * sizeof(int32_t);
     const size_t back_bytes = pose_clearance ? id_off : pc_off;
-    int rc;
-    if ((rc = grow(cl, cl->h_in, cl->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(cl, cl->d_in, cl->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(cl, cl->h_out, cl->cap_h_out, back_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(cl, cl->d_out, cl->cap_d_out, dev_bytes, false)) != RP_OK) return rc;
-    double *h_poses = static_cast<double *>(cl->h_in);
+    const int rc = grow_call(cl, "rp_clearance_query", in_bytes, back_bytes, dev_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_poses = static_cast<double *>(cl->h_in.p);
     std::memcpy(h_poses, x, P * sizeof(double));
     std::memcpy(h_poses + P, y, P * sizeof(double));
     std::memcpy(h_poses + 2 * P, theta, P * sizeof(double));
     if (len) std::memcpy(h_poses + 3 * P, len, Kz * sizeof(int32_t));
-    CL_TRY(cl, hipMemcpyAsync(cl->d_in, cl->h_in, in_bytes, hipMemcpyHostToDevice, cl->stream));
-    char *d_out = static_cast<char *>(cl->d_out);
+    RP_TRY(cl, hipMemcpyAsync(cl->d_in.p, cl->h_in.p, in_bytes, hipMemcpyHostToDevice, cl->stream));
+    char *d_out = static_cast<char *>(cl->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(d_out);
     double *d_minc = reinterpret_cast<double *>(d_out + minc_off), *d_pc = reinterpret_cast<double *>(d_out + pc_off);
     int32_t *d_minp = reinterpret_cast<int32_t *>(d_out + minp_off), *d_near = reinterpret_cast<int32_t *>(d_out + near_off);
     int32_t *d_id = reinterpret_cast<int32_t *>(d_out + id_off);
-    const double *d_poses = static_cast<const double *>(cl->d_in);
+    const double *d_poses = static_cast<const double *>(cl->d_in.p);
     const int32_t *d_len = len ? reinterpret_cast<const int32_t *>(d_poses + 3 * P) : nullptr;
     const int nchunk = (n_poses + 63) / 64;
     const long long waves = (long long)K * nchunk;
@@ -461,15 +354,15 @@ int rp_clearance_query(rp_clearance *cl, const rp_params *p, int64_t K, int32_t 
     const auto kernel = in_lds ? rp_clearance_pose_kernel<true> : rp_clearance_pose_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(CL_BLOCK), 0, cl->stream, cl->tb, d_poses, d_len, (int)K, (int)n_poses, nchunk, p->wb_rear_axle,
                        0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor, cutoff, d_pc, d_id);
-    CL_TRY(cl, hipGetLastError());
+    RP_TRY(cl, hipGetLastError());
     hipLaunchKernelGGL(rp_clearance_traj_kernel, dim3((unsigned)((K + CL_WAVES - 1) / CL_WAVES)), dim3(CL_BLOCK), 0, cl->stream, (int)K, (int)n_poses,
                        d_pc, d_id, d_minc, d_minp, d_near);
-    CL_TRY(cl, hipGetLastError());
+    RP_TRY(cl, hipGetLastError());
     hipLaunchKernelGGL(rp_clearance_final_kernel, dim3(1), dim3(CL_FINAL_BLOCK), 0, cl->stream, (long long)K, d_minc, margin, d_red);
-    CL_TRY(cl, hipGetLastError());
-    CL_TRY(cl, hipMemcpyAsync(cl->h_out, cl->d_out, back_bytes, hipMemcpyDeviceToHost, cl->stream));
-    CL_TRY(cl, hipStreamSynchronize(cl->stream));
-    const char *h_out = static_cast<const char *>(cl->h_out);
+    RP_TRY(cl, hipGetLastError());
+    RP_TRY(cl, hipMemcpyAsync(cl->h_out.p, cl->d_out.p, back_bytes, hipMemcpyDeviceToHost, cl->stream));
+    RP_TRY(cl, hipStreamSynchronize(cl->stream));
+    const char *h_out = static_cast<const char *>(cl->h_out.p);
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (first_clear) *first_clear = h_red[0] < (unsigned long long)K ? (int64_t)h_red[0] : -1;
     if (n_below) *n_below = (int64_t)h_red[1];

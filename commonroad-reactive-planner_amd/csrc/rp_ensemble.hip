@@ -3,8 +3,8 @@
 // K given trajectories x n poses against M sampled predictions ("members") of the dynamic obstacles, in one call.  The narrow
 // phase is the planner's (rp_device.h: Obb, obb_obb, obb_tri, obb_circ, merge_swept) behind the bounding-circle pre-test of
 // rp_check.hip, so a verdict per (trajectory, member) is the boolean rp_checker_check and the planner's kernels produce.  The
-// static row layout and the host-side packing of rp_check.hip are restated here on purpose: that file and its library stay
-// untouched, and the two libraries share no object code.
+// tables and their host-side packing are those of rp_obstacle_tables.h; the walk of the static rows is restated here, and the two
+// libraries share no object code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,13 +14,15 @@
 #include <vector>
 
 #include "rp_device.h"
+#include "rp_obstacle_tables.h"   // the tables' layout and host builder: shared with the checker, the clearance query and the picks
+#include "rp_session.h"           // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_ensemble.h"
 
 namespace {
 
 constexpr int EN_BLOCK = 256;                   // four wavefronts per workgroup
 constexpr int EN_WAVES = EN_BLOCK / 64;
-constexpr int EN_ROW = 10;                      // doubles per static row (below)
+constexpr int EN_ROW = OT_ROW;                  // doubles per static row (rp_obstacle_tables.h)
 constexpr int EN_LDS_ROWS = 128;                // static rows staged in LDS (10 KiB per workgroup); more: read from device memory
 constexpr int32_t EN_NONE = 0x7f7f7f7f;         // "no hit yet" of the first-hit matrices (a byte fill), above every pose index
 // Members one wavefront tests side by side (the member blocks are the grid's y dimension).  A larger block shares the rectangles
@@ -37,11 +39,9 @@ constexpr int EN_RED_PER_WAVE = 64 / (EN_RED_BLOCK / 64);
 
 static_assert(EN_MEMBER_BLOCK >= 1, "a wavefront walks at least one member");
 
-// Static shapes as ONE table, rectangles first, then triangles, then circles; every lane of a wavefront reads the same row
-// (a broadcast from LDS, or a scalar load).  Row: [0..5] the shape -- rectangle cx, cy, ux, uy, hl, hw | triangle x1 .. y3 |
-// circle cx, cy, r -- then [6..8] its bounding circle cx, cy, r and one double of padding.
-// Dynamic rectangles: per member struct-of-arrays planes [M][7][n_dyn][n_steps] cx, cy, ux, uy, hl, hw, r_bound (cx = NaN:
-// absent), so that the lanes of a wavefront -- consecutive time indices -- read consecutive addresses.
+// The tables of rp_obstacle_tables.h, the dynamic planes once per member: [M][7][n_dyn][n_steps].  Every lane of a wavefront reads
+// the same static row (a broadcast from LDS, or a scalar load); the dynamic planes are laid out so that the lanes of a wavefront --
+// consecutive time indices -- read consecutive addresses.
 struct EnTables {
     const double *stat;
     const double *dyn;
@@ -244,128 +244,31 @@ __global__ __launch_bounds__(EN_RED_BLOCK) void rp_ensemble_reduce_kernel(int K,
 
 }  // namespace
 
-struct rp_ensemble {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_ensemble : RpSession {
     EnTables tb = {nullptr, nullptr, 0, 0, 0, 1, 0, 0, 0};   // no static shapes, one member without dynamic obstacles
-    double *d_stat = nullptr, *d_dyn = nullptr;
-    // poses (and lengths) of a call: pinned host block and its device copy; results: a device block for everything the kernels
-    // write and a pinned host block for what the caller asked back.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_stat, d_dyn;
 };
-
-namespace {
-
-int fail(rp_ensemble *en, int code, const std::string &msg) {
-    en->err = msg;
-    return code;
-}
-
-#define EN_TRY(en, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(en, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int upload(rp_ensemble *en, double *&dst, const std::vector<double> &src) {
-    if (dst) { EN_TRY(en, hipFree(dst)); dst = nullptr; }
-    if (src.empty()) return RP_OK;
-    EN_TRY(en, hipMalloc((void **)&dst, src.size() * sizeof(double)));
-    EN_TRY(en, hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
-    return RP_OK;
-}
-
-int grow(rp_ensemble *en, void *&block, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (block) { EN_TRY(en, pinned ? hipHostFree(block) : hipFree(block)); block = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&block, want, hipHostMallocDefault) : hipMalloc(&block, want)) != hipSuccess) {
-        block = nullptr;
-        return fail(en, RP_ENOMEM, pinned ? "rp_ensemble_check: pinned host memory" : "rp_ensemble_check: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
 int rp_ensemble_abi_version(void) { return RP_ENSEMBLE_ABI_VERSION; }
 
-int rp_ensemble_create(rp_ensemble **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_ensemble *en = new (std::nothrow) rp_ensemble();
-    if (!en) return RP_ENOMEM;
-    *out = en;   // returned even on failure so that rp_ensemble_last_error works; the caller destroys it
-    en->device = device;
-    int ndev = 0;
-    EN_TRY(en, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(en, RP_EINVAL, "no such HIP device");
-    EN_TRY(en, hipSetDevice(device));
-    EN_TRY(en, hipStreamCreateWithFlags(&en->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_ensemble_create(rp_ensemble **out, int device) { return session_create(out, device); }
 
-void rp_ensemble_destroy(rp_ensemble *en) {
-    if (!en) return;
-    (void)hipSetDevice(en->device);
-    if (en->stream) (void)hipStreamSynchronize(en->stream);
-    void *dev[] = {en->d_stat, en->d_dyn, en->d_in, en->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (en->h_in) (void)hipHostFree(en->h_in);
-    if (en->h_out) (void)hipHostFree(en->h_out);
-    if (en->stream) (void)hipStreamDestroy(en->stream);
-    delete en;
-}
+void rp_ensemble_destroy(rp_ensemble *en) { session_destroy(en); }
 
-const char *rp_ensemble_last_error(const rp_ensemble *en) { return en ? en->err.c_str() : "null ensemble"; }
+const char *rp_ensemble_last_error(const rp_ensemble *en) { return session_last_error(en, "null ensemble"); }
 
 int rp_ensemble_set_static(rp_ensemble *en, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ,
                            const double *circ) {
     if (!en) return RP_EINVAL;
     if (!en->stream) return fail(en, RP_ESTATE, "rp_ensemble_set_static: the object has no device (rp_ensemble_create failed)");
-    if (n_sobb < 0 || n_tri < 0 || n_circ < 0 || (n_sobb && !sobb) || (n_tri && !tri) || (n_circ && !circ))
-        return fail(en, RP_EINVAL, "rp_ensemble_set_static: negative count or null table");
-    if ((int64_t)n_sobb + n_tri + n_circ > INT32_MAX / EN_ROW) return fail(en, RP_EINVAL, "rp_ensemble_set_static: too many static shapes");
-    EN_TRY(en, hipSetDevice(en->device));
-    EN_TRY(en, hipStreamSynchronize(en->stream));
-    std::vector<double> a;
-    try {
-        a.assign(((size_t)n_sobb + (size_t)n_tri + (size_t)n_circ) * EN_ROW, 0.0);
-    } catch (const std::bad_alloc &) {
-        return fail(en, RP_ENOMEM, "rp_ensemble_set_static: host memory");
-    }
-    double *r = a.data();
-    for (int j = 0; j < n_sobb; ++j, r += EN_ROW) {   // (ux, uy from the host's cos / sin, as rp_checker_set_obstacles)
-        const double *o = sobb + 5 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = std::cos(o[2]); r[3] = std::sin(o[2]); r[4] = o[3]; r[5] = o[4];
-        r[6] = o[0]; r[7] = o[1]; r[8] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-    }
-    for (int j = 0; j < n_tri; ++j, r += EN_ROW) {
-        const double *o = tri + 6 * (size_t)j;
-        for (int q = 0; q < 6; ++q) r[q] = o[q];
-        const double bx = (o[0] + o[2] + o[4]) / 3.0, by = (o[1] + o[3] + o[5]) / 3.0;
-        double rr = 0.0;
-        for (int q = 0; q < 3; ++q) rr = std::fmax(rr, std::hypot(o[2 * q] - bx, o[2 * q + 1] - by));
-        r[6] = bx; r[7] = by; r[8] = rr;
-    }
-    for (int j = 0; j < n_circ; ++j, r += EN_ROW) {
-        const double *o = circ + 3 * (size_t)j;
-        r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
-        r[6] = o[0]; r[7] = o[1]; r[8] = o[2];
-    }
-    en->tb.stat = nullptr;   // (a failed upload leaves no static shapes, never half of the new ones)
-    en->tb.n_sobb = en->tb.n_tri = en->tb.n_circ = 0;
-    int rc;
-    if ((rc = upload(en, en->d_stat, a)) != RP_OK) return rc;
-    en->tb.stat = en->d_stat;
+    std::vector<double> a, none;
+    std::string msg;
+    int rc = ot_build("rp_ensemble_set_static", n_sobb, sobb, n_tri, tri, n_circ, circ, 0, 0, nullptr, a, none, msg);
+    if (rc != RP_OK) return fail(en, rc, msg);
+    if ((rc = replace_tables(en, {{&en->d_stat, &a}})) != RP_OK) return rc;
+    en->tb.stat = en->d_stat.p;
     en->tb.n_sobb = n_sobb; en->tb.n_tri = n_tri; en->tb.n_circ = n_circ;
     return RP_OK;
 }
@@ -379,30 +282,17 @@ int rp_ensemble_set_members(rp_ensemble *en, int32_t n_members, int32_t n_dyn, i
     if (plane64 > RP_ENSEMBLE_MAX_DYN_ROWS || (int64_t)n_members * plane64 > RP_ENSEMBLE_MAX_DYN_ROWS)
         return fail(en, RP_EINVAL, "rp_ensemble_set_members: n_members * n_dyn * n_steps beyond RP_ENSEMBLE_MAX_DYN_ROWS");
     if (plane64 && !dyn) return fail(en, RP_EINVAL, "rp_ensemble_set_members: null table");
-    EN_TRY(en, hipSetDevice(en->device));
-    EN_TRY(en, hipStreamSynchronize(en->stream));
     const size_t plane = (size_t)plane64;
-    std::vector<double> e;
+    std::vector<double> e;   // [M][7][n_dyn * n_steps]: member by member the planes of rp_obstacle_tables.h
     try {
         e.assign((size_t)n_members * 7 * plane, 0.0);
     } catch (const std::bad_alloc &) {
         return fail(en, RP_ENOMEM, "rp_ensemble_set_members: host memory");
     }
-    for (size_t m = 0; m < (size_t)n_members; ++m) {
-        double *q = e.data() + m * 7 * plane;
-        for (size_t at = 0; at < plane; ++at) {
-            const double *o = dyn + 5 * (m * plane + at);
-            q[at] = o[0]; q[plane + at] = o[1];
-            q[2 * plane + at] = std::cos(o[2]); q[3 * plane + at] = std::sin(o[2]);
-            q[4 * plane + at] = o[3]; q[5 * plane + at] = o[4];
-            q[6 * plane + at] = std::sqrt(o[3] * o[3] + o[4] * o[4]);
-        }
-    }
-    en->tb.dyn = nullptr;   // (a failed upload leaves one member without dynamic obstacles, never half of the new ones)
-    en->tb.n_members = 1; en->tb.n_dyn = en->tb.n_steps = en->tb.dyn_t0 = 0;
-    int rc;
-    if ((rc = upload(en, en->d_dyn, e)) != RP_OK) return rc;
-    en->tb.dyn = en->d_dyn;
+    for (size_t m = 0; m < (size_t)n_members; ++m) ot_dynamic_planes(e.data() + m * 7 * plane, plane, dyn + 5 * m * plane);
+    const int rc = replace_tables(en, {{&en->d_dyn, &e}});
+    if (rc != RP_OK) return rc;
+    en->tb.dyn = en->d_dyn.p;
     en->tb.n_members = n_members; en->tb.n_dyn = plane ? n_dyn : 0; en->tb.n_steps = plane ? n_steps : 0; en->tb.dyn_t0 = dyn_t0;
     return RP_OK;
 }
@@ -432,7 +322,7 @@ int rp_ensemble_check(rp_ensemble *en, const rp_params *p, uint32_t mode, int64_
         return RP_OK;
     }
     if (!en->stream) return fail(en, RP_ESTATE, "rp_ensemble_check: the object has no device (rp_ensemble_create failed)");
-    EN_TRY(en, hipSetDevice(en->device));
+    RP_TRY(en, hipSetDevice(en->device));
     const size_t P = (size_t)K * (size_t)n_poses, V = (size_t)K * (size_t)M;
     const size_t in_bytes = 3 * P * sizeof(double) + (len ? (size_t)K * sizeof(int32_t) : 0);
     // device results: red[2] | members_hit [K] | (16-byte boundary) first_pose [K][M] | first_seg [K][M]
@@ -442,24 +332,21 @@ int rp_ensemble_check(rp_ensemble *en, const rp_params *p, uint32_t mode, int64_
     // host results: the head, then the matrices the caller asked for
     const size_t h_pose_off = head_bytes, h_seg_off = head_bytes + (first_pose_hit ? mat_bytes : 0);
     const size_t h_out_bytes = h_seg_off + (first_segment_hit ? mat_bytes : 0);
-    int rc;
-    if ((rc = grow(en, en->h_in, en->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(en, en->d_in, en->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(en, en->h_out, en->cap_h_out, h_out_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(en, en->d_out, en->cap_d_out, head_bytes + 2 * mat_bytes, false)) != RP_OK) return rc;
-    double *h_poses = static_cast<double *>(en->h_in);
+    const int rc = grow_call(en, "rp_ensemble_check", in_bytes, h_out_bytes, head_bytes + 2 * mat_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_poses = static_cast<double *>(en->h_in.p);
     std::memcpy(h_poses, x, P * sizeof(double));
     std::memcpy(h_poses + P, y, P * sizeof(double));
     std::memcpy(h_poses + 2 * P, theta, P * sizeof(double));
     if (len) std::memcpy(h_poses + 3 * P, len, (size_t)K * sizeof(int32_t));
-    EN_TRY(en, hipMemcpyAsync(en->d_in, en->h_in, in_bytes, hipMemcpyHostToDevice, en->stream));
-    char *d_out = static_cast<char *>(en->d_out);
+    RP_TRY(en, hipMemcpyAsync(en->d_in.p, en->h_in.p, in_bytes, hipMemcpyHostToDevice, en->stream));
+    char *d_out = static_cast<char *>(en->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(d_out);
     int32_t *d_count = reinterpret_cast<int32_t *>(d_out + count_off);
     int32_t *d_first_pose = reinterpret_cast<int32_t *>(d_out + head_bytes), *d_first_seg = d_first_pose + V;
-    if (mode == (RP_TRAJ_POSES | RP_TRAJ_SWEPT)) EN_TRY(en, hipMemsetAsync(d_first_pose, 0x7f, 2 * mat_bytes, en->stream));
-    else EN_TRY(en, hipMemsetAsync((mode & RP_TRAJ_POSES) ? d_first_pose : d_first_seg, 0x7f, mat_bytes, en->stream));
-    const double *d_poses = static_cast<const double *>(en->d_in);
+    if (mode == (RP_TRAJ_POSES | RP_TRAJ_SWEPT)) RP_TRY(en, hipMemsetAsync(d_first_pose, 0x7f, 2 * mat_bytes, en->stream));
+    else RP_TRY(en, hipMemsetAsync((mode & RP_TRAJ_POSES) ? d_first_pose : d_first_seg, 0x7f, mat_bytes, en->stream));
+    const double *d_poses = static_cast<const double *>(en->d_in.p);
     const int32_t *d_len = len ? reinterpret_cast<const int32_t *>(d_poses + 3 * P) : nullptr;
     const int nchunk = (n_poses + 63) / 64;
     const long long waves = (long long)K * nchunk;   // <= 2^24: the grid's x fits
@@ -468,15 +355,15 @@ int rp_ensemble_check(rp_ensemble *en, const rp_params *p, uint32_t mode, int64_
     const auto kernel = in_lds ? rp_ensemble_check_kernel<true> : rp_ensemble_check_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(EN_BLOCK), 0, en->stream, en->tb, d_poses, d_len, (int)K, (int)n_poses, nchunk, mode, p->wb_rear_axle,
                        0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor, d_first_pose, d_first_seg, d_red);
-    EN_TRY(en, hipGetLastError());
+    RP_TRY(en, hipGetLastError());
     hipLaunchKernelGGL(rp_ensemble_reduce_kernel, dim3((unsigned)((K + 63) / 64)), dim3(EN_RED_BLOCK), 0, en->stream, (int)K, M, mode,
                        (int)max_members_hit, d_first_pose, d_first_seg, d_count, d_red);
-    EN_TRY(en, hipGetLastError());
-    char *h_out = static_cast<char *>(en->h_out);
-    EN_TRY(en, hipMemcpyAsync(h_out, d_out, count_off + (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, en->stream));
-    if (first_pose_hit) EN_TRY(en, hipMemcpyAsync(h_out + h_pose_off, d_first_pose, mat_bytes, hipMemcpyDeviceToHost, en->stream));
-    if (first_segment_hit) EN_TRY(en, hipMemcpyAsync(h_out + h_seg_off, d_first_seg, mat_bytes, hipMemcpyDeviceToHost, en->stream));
-    EN_TRY(en, hipStreamSynchronize(en->stream));
+    RP_TRY(en, hipGetLastError());
+    char *h_out = static_cast<char *>(en->h_out.p);
+    RP_TRY(en, hipMemcpyAsync(h_out, d_out, count_off + (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, en->stream));
+    if (first_pose_hit) RP_TRY(en, hipMemcpyAsync(h_out + h_pose_off, d_first_pose, mat_bytes, hipMemcpyDeviceToHost, en->stream));
+    if (first_segment_hit) RP_TRY(en, hipMemcpyAsync(h_out + h_seg_off, d_first_seg, mat_bytes, hipMemcpyDeviceToHost, en->stream));
+    RP_TRY(en, hipStreamSynchronize(en->stream));
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (first_free) *first_free = h_red[0] < (unsigned long long)K ? (int64_t)h_red[0] : -1;
     if (n_over) *n_over = (int64_t)h_red[1];

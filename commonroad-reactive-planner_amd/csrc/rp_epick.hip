@@ -23,9 +23,10 @@
 #include <string>
 #include <vector>
 
-#include "rp_check_rules.h"   // the obstacle tables, cc.collide and both tests of a chunk: shared with rp_check.hip and rp_pick.hip
+#include "rp_check_rules.h"   // the obstacle tables and their builder, cc.collide and both tests of a chunk: shared with rp_check.hip and rp_pick.hip
 #include "rp_lift_rules.h"    // the segment row, the segment search, the step's checks: shared with rp_lift.hip and rp_pick.hip
 #include "rp_pick_cost.h"     // the cost's scalars and the terms of a pose: shared with rp_pick.hip
+#include "rp_session.h"       // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_epick.h"
 
 namespace {
@@ -365,108 +366,34 @@ __global__ __launch_bounds__(EP_FINAL_BLOCK) void rp_epick_final_kernel(long lon
 
 }  // namespace
 
-struct rp_epick {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_epick : RpSession {
     LfTable tb = {nullptr, 0, 0, 0.0, 0.0, 0.0};
     CkTables stat = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};   // the static shapes alone: no dynamic rows
     EpMembers mb = {nullptr, nullptr, 1, 0, 0, 0};          // one member without dynamic obstacles; its weight (1.0) comes with create
-    double *d_rows = nullptr, *d_stat = nullptr, *d_dyn = nullptr, *d_weight = nullptr;
-    // inputs of a call: pinned host block and its device copy; the results on the device and a pinned host block for the part of
-    // them a call asks for.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_rows, d_stat, d_dyn, d_weight;
 };
-
-namespace {
-
-int fail(rp_epick *ep, int code, const std::string &msg) {
-    ep->err = msg;
-    return code;
-}
-
-#define EP_TRY(ep, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ep, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int grow(rp_epick *ep, void *&buf, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (buf) { EP_TRY(ep, pinned ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&buf, want, hipHostMallocDefault) : hipMalloc(&buf, want)) != hipSuccess) {
-        buf = nullptr;
-        return fail(ep, RP_ENOMEM, pinned ? "rp_epick: pinned host memory" : "rp_epick: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-// a new table beside the old one; the old one is freed only once the new one is whole
-int upload(rp_epick *ep, double *&fresh, const std::vector<double> &src) {
-    fresh = nullptr;
-    if (src.empty()) return RP_OK;
-    EP_TRY(ep, hipMalloc((void **)&fresh, src.size() * sizeof(double)));
-    const hipError_t e = hipMemcpy(fresh, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        fresh = nullptr;
-        return fail(ep, RP_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    return RP_OK;
-}
-
-size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
-
-}  // namespace
 
 extern "C" {
 
 int rp_epick_abi_version(void) { return RP_EPICK_ABI_VERSION; }
 
 int rp_epick_create(rp_epick **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_epick *ep = new (std::nothrow) rp_epick();
-    if (!ep) return RP_ENOMEM;
-    *out = ep;   // returned even on failure so that rp_epick_last_error works; the caller destroys it
-    ep->device = device;
-    int ndev = 0;
-    EP_TRY(ep, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ep, RP_EINVAL, "no such HIP device");
-    EP_TRY(ep, hipSetDevice(device));
-    hipStream_t stream = nullptr;
-    EP_TRY(ep, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const double one = 1.0;   // the weight of the one member a fresh object has
-    hipError_t e = hipMalloc((void **)&ep->d_weight, sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(ep->d_weight, &one, sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipStreamDestroy(stream);   // (without a stream the object has no device: every later call says so)
-        return fail(ep, RP_EHIP, std::string("rp_epick_create: ") + hipGetErrorString(e));
+    int rc = session_create(out, device);
+    if (rc != RP_OK) return rc;
+    rp_epick *ep = *out;
+    const std::vector<double> one(1, 1.0);   // the weight of the one member a fresh object has
+    if ((rc = replace_tables(ep, {{&ep->d_weight, &one}})) != RP_OK) {
+        (void)hipStreamDestroy(ep->stream);   // (without a stream the object has no device: every later call says so)
+        ep->stream = nullptr;
+        return rc;
     }
-    ep->mb.weight = ep->d_weight;
-    ep->stream = stream;
+    ep->mb.weight = ep->d_weight.p;
     return RP_OK;
 }
 
-void rp_epick_destroy(rp_epick *ep) {
-    if (!ep) return;
-    (void)hipSetDevice(ep->device);
-    if (ep->stream) (void)hipStreamSynchronize(ep->stream);
-    void *dev[] = {ep->d_rows, ep->d_stat, ep->d_dyn, ep->d_weight, ep->d_in, ep->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (ep->h_in) (void)hipHostFree(ep->h_in);
-    if (ep->h_out) (void)hipHostFree(ep->h_out);
-    if (ep->stream) (void)hipStreamDestroy(ep->stream);
-    delete ep;
-}
+void rp_epick_destroy(rp_epick *ep) { session_destroy(ep); }
 
-const char *rp_epick_last_error(const rp_epick *ep) { return ep ? ep->err.c_str() : "null epick object"; }
+const char *rp_epick_last_error(const rp_epick *ep) { return session_last_error(ep, "null epick object"); }
 
 int rp_epick_set_reference(rp_epick *ep, int32_t n, const double *ref_xy, const double *ref_pos, const double *ref_theta, const double *ref_curv,
                            const double *ref_curv_d, double proj_domain_d_limit) {
@@ -474,34 +401,22 @@ int rp_epick_set_reference(rp_epick *ep, int32_t n, const double *ref_xy, const 
     if (!ep->stream) return fail(ep, RP_ESTATE, "rp_epick_set_reference: the object has no device (rp_epick_create failed)");
     std::vector<double> rows;
     std::string msg;
-    const int rc = lf_build_rows("rp_epick_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
+    int rc = lf_build_rows("rp_epick_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
     if (rc != RP_OK) return fail(ep, rc, msg);
-    EP_TRY(ep, hipSetDevice(ep->device));
-    EP_TRY(ep, hipStreamSynchronize(ep->stream));
-    double *fresh = nullptr;
-    int up;
-    if ((up = upload(ep, fresh, rows)) != RP_OK) return up;
-    if (ep->d_rows) (void)hipFree(ep->d_rows);
-    ep->d_rows = fresh;
-    ep->tb = {ep->d_rows, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
+    if ((rc = replace_tables(ep, {{&ep->d_rows, &rows}})) != RP_OK) return rc;
+    ep->tb = {ep->d_rows.p, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
     return RP_OK;
 }
 
 int rp_epick_set_static(rp_epick *ep, int32_t n_sobb, const double *sobb, int32_t n_tri, const double *tri, int32_t n_circ, const double *circ) {
     if (!ep) return RP_EINVAL;
     if (!ep->stream) return fail(ep, RP_ESTATE, "rp_epick_set_static: the object has no device (rp_epick_create failed)");
-    std::vector<double> a, e;
+    std::vector<double> a, none;
     std::string msg;
-    const int rc = ck_build_tables("rp_epick_set_static", n_sobb, sobb, n_tri, tri, n_circ, circ, 0, 0, nullptr, a, e, msg);
+    int rc = ot_build("rp_epick_set_static", n_sobb, sobb, n_tri, tri, n_circ, circ, 0, 0, nullptr, a, none, msg);
     if (rc != RP_OK) return fail(ep, rc, msg);
-    EP_TRY(ep, hipSetDevice(ep->device));
-    EP_TRY(ep, hipStreamSynchronize(ep->stream));
-    double *fresh = nullptr;
-    int up;
-    if ((up = upload(ep, fresh, a)) != RP_OK) return up;
-    if (ep->d_stat) (void)hipFree(ep->d_stat);
-    ep->d_stat = fresh;
-    ep->stat = {ep->d_stat, nullptr, n_sobb, n_tri, n_circ, 0, 0, 0};
+    if ((rc = replace_tables(ep, {{&ep->d_stat, &a}})) != RP_OK) return rc;
+    ep->stat = {ep->d_stat.p, nullptr, n_sobb, n_tri, n_circ, 0, 0, 0};
     return RP_OK;
 }
 
@@ -518,36 +433,20 @@ int rp_epick_set_members(rp_epick *ep, int32_t n_members, int32_t n_dyn, int32_t
         for (int32_t m = 0; m < n_members; ++m)
             if (!(weight[m] >= 0.0) || !std::isfinite(weight[m]))
                 return fail(ep, RP_EINVAL, "rp_epick_set_members: weight[" + std::to_string(m) + "] is negative or not finite");
-    // member by member the planes of rp_check_rules.h: each member's part is a table ck_collides reads
+    // member by member the planes of rp_obstacle_tables.h: each member's part is a table ck_collides reads
     const size_t plane = (size_t)plane64;
-    std::vector<double> all, w, a, e;
-    std::string msg;
+    std::vector<double> all, w;
     try {
-        all.reserve((size_t)n_members * 7 * plane);
+        all.assign((size_t)n_members * 7 * plane, 0.0);
         w.assign((size_t)n_members, 1.0);
     } catch (const std::bad_alloc &) {
         return fail(ep, RP_ENOMEM, "rp_epick_set_members: host memory");
     }
     if (weight) std::memcpy(w.data(), weight, (size_t)n_members * sizeof(double));
-    for (size_t m = 0; plane && m < (size_t)n_members; ++m) {
-        const int rc = ck_build_tables("rp_epick_set_members", 0, nullptr, 0, nullptr, 0, nullptr, n_dyn, n_steps, dyn + 5 * m * plane, a, e, msg);
-        if (rc != RP_OK) return fail(ep, rc, msg);
-        all.insert(all.end(), e.begin(), e.end());   // (reserved above: no allocation)
-    }
-    EP_TRY(ep, hipSetDevice(ep->device));
-    EP_TRY(ep, hipStreamSynchronize(ep->stream));
-    double *planes = nullptr, *weights = nullptr;
-    int up;
-    if ((up = upload(ep, planes, all)) != RP_OK) return up;
-    if ((up = upload(ep, weights, w)) != RP_OK) {
-        if (planes) (void)hipFree(planes);
-        return up;
-    }
-    if (ep->d_dyn) (void)hipFree(ep->d_dyn);
-    if (ep->d_weight) (void)hipFree(ep->d_weight);
-    ep->d_dyn = planes;
-    ep->d_weight = weights;
-    ep->mb = {ep->d_dyn, ep->d_weight, n_members, plane ? n_dyn : 0, plane ? n_steps : 0, dyn_t0};
+    for (size_t m = 0; m < (size_t)n_members; ++m) ot_dynamic_planes(all.data() + m * 7 * plane, plane, dyn + 5 * m * plane);
+    const int rc = replace_tables(ep, {{&ep->d_dyn, &all}, {&ep->d_weight, &w}});
+    if (rc != RP_OK) return rc;
+    ep->mb = {ep->d_dyn.p, ep->d_weight.p, n_members, plane ? n_dyn : 0, plane ? n_steps : 0, dyn_t0};
     return RP_OK;
 }
 
@@ -598,7 +497,7 @@ int rp_epick_select(rp_epick *ep, const rp_params *p, const rp_cost *cost, uint3
             for (size_t q = 0; q < (size_t)RP_N_ARRAYS * nz; ++q) best_states[q] = std::nan("");
         return RP_OK;
     }
-    EP_TRY(ep, hipSetDevice(ep->device));
+    RP_TRY(ep, hipSetDevice(ep->device));
     const size_t P = (size_t)K * nz, Kz = (size_t)K, V = Kz * (size_t)M, mat_bytes = V * sizeof(int32_t);
     // inputs: the six planes | theta0? [K] | len? [K]
     const size_t th0_off = 6 * P * sizeof(double), len_off = th0_off + (theta0 ? Kz * sizeof(double) : 0);
@@ -621,18 +520,15 @@ int rp_epick_select(rp_epick *ep, const rp_params *p, const rp_cost *cost, uint3
     // on the host: the front | (8-byte aligned) the matrices asked for | the planes asked for
     const size_t h_fp_off = align8(front_bytes), h_fs_off = h_fp_off + (first_pose_hit ? mat_bytes : 0);
     const size_t h_pl_off = align8(h_fs_off + (first_segment_hit ? mat_bytes : 0));
-    int rc;
-    if ((rc = grow(ep, ep->h_in, ep->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(ep, ep->d_in, ep->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(ep, ep->h_out, ep->cap_h_out, h_pl_off + pl_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(ep, ep->d_out, ep->cap_d_out, dev_bytes, false)) != RP_OK) return rc;
-    char *h_in = static_cast<char *>(ep->h_in);
-    const char *d_in = static_cast<const char *>(ep->d_in);
+    const int rc = grow_call(ep, "rp_epick", in_bytes, h_pl_off + pl_bytes, dev_bytes);
+    if (rc != RP_OK) return rc;
+    char *h_in = static_cast<char *>(ep->h_in.p);
+    const char *d_in = static_cast<const char *>(ep->d_in.p);
     for (int q = 0; q < 6; ++q) std::memcpy(h_in + (size_t)q * P * sizeof(double), planes[q], P * sizeof(double));
     if (theta0) std::memcpy(h_in + th0_off, theta0, Kz * sizeof(double));
     if (len) std::memcpy(h_in + len_off, len, Kz * sizeof(int32_t));
-    EP_TRY(ep, hipMemcpyAsync(ep->d_in, ep->h_in, in_bytes, hipMemcpyHostToDevice, ep->stream));
-    char *dv = static_cast<char *>(ep->d_out);
+    RP_TRY(ep, hipMemcpyAsync(ep->d_in.p, ep->h_in.p, in_bytes, hipMemcpyHostToDevice, ep->stream));
+    char *dv = static_cast<char *>(ep->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(dv);
     double *d_block = reinterpret_cast<double *>(dv + blk_off), *d_cost = reinterpret_cast<double *>(dv + cost_off);
     double *d_risk = reinterpret_cast<double *>(dv + risk_off);
@@ -653,9 +549,9 @@ int rp_epick_select(rp_epick *ep, const rp_params *p, const rp_cost *cost, uint3
     const size_t lds_bytes = rows_in_lds ? (size_t)ep->tb.n_seg * LF_ROW * sizeof(double) : 0;
     hipLaunchKernelGGL(lift, dim3((unsigned)((K + EP_WAVES - 1) / EP_WAVES)), dim3(EP_BLOCK), lds_bytes, ep->stream, ep->tb, kin, cc, d_six, d_len, d_th0,
                        (long long)K, (int)n_poses, (const unsigned long long *)nullptr, (double *)nullptr, all, d_status, d_cost);
-    EP_TRY(ep, hipGetLastError());
+    RP_TRY(ep, hipGetLastError());
     if (mode != 0) {
-        EP_TRY(ep, hipMemsetAsync(d_first_pose, 0x7f, 2 * mat_bytes, ep->stream));
+        RP_TRY(ep, hipMemsetAsync(d_first_pose, 0x7f, 2 * mat_bytes, ep->stream));
         const int nchunk = (n_poses + 63) / 64;
         const long long waves = (long long)K * nchunk;   // <= 2^24: the grid's x fits
         const dim3 grid((unsigned)((waves + EP_WAVES - 1) / EP_WAVES), (unsigned)((M + EP_MEMBER_BLOCK - 1) / EP_MEMBER_BLOCK));
@@ -663,27 +559,27 @@ int rp_epick_select(rp_epick *ep, const rp_params *p, const rp_cost *cost, uint3
         const auto collide = shapes_in_lds ? rp_epick_collide_kernel<true> : rp_epick_collide_kernel<false>;
         hipLaunchKernelGGL(collide, grid, dim3(EP_BLOCK), 0, ep->stream, ep->stat, ep->mb, d_planes, d_len, d_status, (int)K, (int)n_poses, nchunk, mode,
                            p->wb_rear_axle, 0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor, d_first_pose, d_first_seg);
-        EP_TRY(ep, hipGetLastError());
+        RP_TRY(ep, hipGetLastError());
     }
     hipLaunchKernelGGL(rp_epick_risk_kernel, dim3((unsigned)((K + 63) / 64)), dim3(EP_RISK_BLOCK), 0, ep->stream, (int)K, M, mode, max_risk, ep->mb.weight,
                        d_status, d_first_pose, d_first_seg, d_hit, d_risk);
-    EP_TRY(ep, hipGetLastError());
+    RP_TRY(ep, hipGetLastError());
     hipLaunchKernelGGL(rp_epick_final_kernel, dim3(1), dim3(EP_FINAL_BLOCK), 0, ep->stream, (long long)K, mode, d_status, d_cost, d_hit, d_risk, d_red);
-    EP_TRY(ep, hipGetLastError());
+    RP_TRY(ep, hipGetLastError());
     if (best_states) {
         EpPlanes rows;
         for (int q = 0; q < LF_PLANES; ++q) rows.plane[q] = d_block + (size_t)EP_PLANE_ROW[q] * nz;
         hipLaunchKernelGGL(lift, dim3(1), dim3(EP_BLOCK), lds_bytes, ep->stream, ep->tb, kin, cc, d_six, d_len, d_th0, (long long)K, (int)n_poses,
                            (const unsigned long long *)d_red, d_block, rows, (uint32_t *)nullptr, (double *)nullptr);
-        EP_TRY(ep, hipGetLastError());
+        RP_TRY(ep, hipGetLastError());
     }
-    char *h_out = static_cast<char *>(ep->h_out);
-    EP_TRY(ep, hipMemcpyAsync(h_out, dv, front_bytes, hipMemcpyDeviceToHost, ep->stream));
-    if (first_pose_hit) EP_TRY(ep, hipMemcpyAsync(h_out + h_fp_off, d_first_pose, mat_bytes, hipMemcpyDeviceToHost, ep->stream));
-    if (first_segment_hit) EP_TRY(ep, hipMemcpyAsync(h_out + h_fs_off, d_first_seg, mat_bytes, hipMemcpyDeviceToHost, ep->stream));
+    char *h_out = static_cast<char *>(ep->h_out.p);
+    RP_TRY(ep, hipMemcpyAsync(h_out, dv, front_bytes, hipMemcpyDeviceToHost, ep->stream));
+    if (first_pose_hit) RP_TRY(ep, hipMemcpyAsync(h_out + h_fp_off, d_first_pose, mat_bytes, hipMemcpyDeviceToHost, ep->stream));
+    if (first_segment_hit) RP_TRY(ep, hipMemcpyAsync(h_out + h_fs_off, d_first_seg, mat_bytes, hipMemcpyDeviceToHost, ep->stream));
     if (pl_bytes)
-        EP_TRY(ep, hipMemcpyAsync(h_out + h_pl_off, dv + pl_off + (size_t)pl_first * P * sizeof(double), pl_bytes, hipMemcpyDeviceToHost, ep->stream));
-    EP_TRY(ep, hipStreamSynchronize(ep->stream));
+        RP_TRY(ep, hipMemcpyAsync(h_out + h_pl_off, dv + pl_off + (size_t)pl_first * P * sizeof(double), pl_bytes, hipMemcpyDeviceToHost, ep->stream));
+    RP_TRY(ep, hipStreamSynchronize(ep->stream));
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (result) {
         const bool any = h_red[RED_BEST] < (unsigned long long)K;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rp_lift_rules.h"   // the segment row, the segment search, the step's checks: shared with rp_pick.hip
+#include "rp_session.h"      // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_lift.h"
 
 namespace {
@@ -168,82 +169,20 @@ __global__ __launch_bounds__(LF_FINAL_BLOCK) void rp_lift_outside_kernel(long lo
 
 }  // namespace
 
-struct rp_lift {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_lift : RpSession {
     LfTable tb = {nullptr, 0, 0, 0.0, 0.0, 0.0};
-    double *d_rows = nullptr;
-    // inputs of a call: pinned host block and its device copy; the results on the device and a pinned host block for the part of
-    // them a call asks for.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_rows;
 };
-
-namespace {
-
-int fail(rp_lift *lf, int code, const std::string &msg) {
-    lf->err = msg;
-    return code;
-}
-
-#define LF_TRY(lf, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(lf, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int grow(rp_lift *lf, void *&buf, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (buf) { LF_TRY(lf, pinned ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&buf, want, hipHostMallocDefault) : hipMalloc(&buf, want)) != hipSuccess) {
-        buf = nullptr;
-        return fail(lf, RP_ENOMEM, pinned ? "rp_lift: pinned host memory" : "rp_lift: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
-
-}  // namespace
 
 extern "C" {
 
 int rp_lift_abi_version(void) { return RP_LIFT_ABI_VERSION; }
 
-int rp_lift_create(rp_lift **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_lift *lf = new (std::nothrow) rp_lift();
-    if (!lf) return RP_ENOMEM;
-    *out = lf;   // returned even on failure so that rp_lift_last_error works; the caller destroys it
-    lf->device = device;
-    int ndev = 0;
-    LF_TRY(lf, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(lf, RP_EINVAL, "no such HIP device");
-    LF_TRY(lf, hipSetDevice(device));
-    LF_TRY(lf, hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_lift_create(rp_lift **out, int device) { return session_create(out, device); }
 
-void rp_lift_destroy(rp_lift *lf) {
-    if (!lf) return;
-    (void)hipSetDevice(lf->device);
-    if (lf->stream) (void)hipStreamSynchronize(lf->stream);
-    void *dev[] = {lf->d_rows, lf->d_in, lf->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (lf->h_in) (void)hipHostFree(lf->h_in);
-    if (lf->h_out) (void)hipHostFree(lf->h_out);
-    if (lf->stream) (void)hipStreamDestroy(lf->stream);
-    delete lf;
-}
+void rp_lift_destroy(rp_lift *lf) { session_destroy(lf); }
 
-const char *rp_lift_last_error(const rp_lift *lf) { return lf ? lf->err.c_str() : "null lift object"; }
+const char *rp_lift_last_error(const rp_lift *lf) { return session_last_error(lf, "null lift object"); }
 
 int rp_lift_set_reference(rp_lift *lf, int32_t n, const double *ref_xy, const double *ref_pos, const double *ref_theta, const double *ref_curv,
                           const double *ref_curv_d, double proj_domain_d_limit) {
@@ -253,13 +192,9 @@ int rp_lift_set_reference(rp_lift *lf, int32_t n, const double *ref_xy, const do
     std::string msg;
     const int built = lf_build_rows("rp_lift_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
     if (built != RP_OK) return fail(lf, built, msg);
-    LF_TRY(lf, hipSetDevice(lf->device));
-    LF_TRY(lf, hipStreamSynchronize(lf->stream));
-    lf->tb = {nullptr, 0, 0, 0.0, 0.0, 0.0};   // (a failed upload leaves no table, never half of the new one)
-    if (lf->d_rows) { LF_TRY(lf, hipFree(lf->d_rows)); lf->d_rows = nullptr; }
-    LF_TRY(lf, hipMalloc((void **)&lf->d_rows, rows.size() * sizeof(double)));
-    LF_TRY(lf, hipMemcpy(lf->d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    lf->tb = {lf->d_rows, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
+    const int rc = replace_tables(lf, {{&lf->d_rows, &rows}});
+    if (rc != RP_OK) return rc;
+    lf->tb = {lf->d_rows.p, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
     return RP_OK;
 }
 
@@ -273,36 +208,33 @@ int rp_lift_points(rp_lift *lf, int64_t n_points, const double *s, const double 
         if (n_outside) *n_outside = 0;
         return RP_OK;
     }
-    LF_TRY(lf, hipSetDevice(lf->device));
+    RP_TRY(lf, hipSetDevice(lf->device));
     const size_t P = (size_t)n_points;
     const size_t in_bytes = 2 * P * sizeof(double);
     // results on the device: scalar | x [P] | y [P] | segment [P]
     const size_t x_off = 8 * sizeof(unsigned long long), y_off = x_off + P * sizeof(double), seg_off = y_off + P * sizeof(double);
     const size_t out_bytes = seg_off + P * sizeof(int32_t);
-    int rc;
-    if ((rc = grow(lf, lf->h_in, lf->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->d_in, lf->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->h_out, lf->cap_h_out, out_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->d_out, lf->cap_d_out, out_bytes, false)) != RP_OK) return rc;
-    double *h_in = static_cast<double *>(lf->h_in);
+    const int rc = grow_call(lf, "rp_lift", in_bytes, out_bytes, out_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_in = static_cast<double *>(lf->h_in.p);
     std::memcpy(h_in, s, P * sizeof(double));
     std::memcpy(h_in + P, d, P * sizeof(double));
-    LF_TRY(lf, hipMemcpyAsync(lf->d_in, lf->h_in, in_bytes, hipMemcpyHostToDevice, lf->stream));
-    const double *d_s = static_cast<const double *>(lf->d_in);
-    char *dv = static_cast<char *>(lf->d_out);
+    RP_TRY(lf, hipMemcpyAsync(lf->d_in.p, lf->h_in.p, in_bytes, hipMemcpyHostToDevice, lf->stream));
+    const double *d_s = static_cast<const double *>(lf->d_in.p);
+    char *dv = static_cast<char *>(lf->d_out.p);
     int32_t *d_seg = reinterpret_cast<int32_t *>(dv + seg_off);
     const bool in_lds = lf->tb.n_seg <= LF_LDS_ROWS;
     const auto kernel = in_lds ? rp_lift_points_kernel<true> : rp_lift_points_kernel<false>;
     const size_t lds_bytes = in_lds ? (size_t)lf->tb.n_seg * LF_ROW * sizeof(double) : 0;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n_points + LF_BLOCK - 1) / LF_BLOCK)), dim3(LF_BLOCK), lds_bytes, lf->stream, lf->tb, d_s, d_s + P,
                        (long long)n_points, reinterpret_cast<double *>(dv + x_off), reinterpret_cast<double *>(dv + y_off), d_seg);
-    LF_TRY(lf, hipGetLastError());
+    RP_TRY(lf, hipGetLastError());
     hipLaunchKernelGGL(rp_lift_outside_kernel, dim3(1), dim3(LF_FINAL_BLOCK), 0, lf->stream, (long long)n_points, d_seg,
                        reinterpret_cast<unsigned long long *>(dv));
-    LF_TRY(lf, hipGetLastError());
-    LF_TRY(lf, hipMemcpyAsync(lf->h_out, lf->d_out, out_bytes, hipMemcpyDeviceToHost, lf->stream));
-    LF_TRY(lf, hipStreamSynchronize(lf->stream));
-    const char *h_out = static_cast<const char *>(lf->h_out);
+    RP_TRY(lf, hipGetLastError());
+    RP_TRY(lf, hipMemcpyAsync(lf->h_out.p, lf->d_out.p, out_bytes, hipMemcpyDeviceToHost, lf->stream));
+    RP_TRY(lf, hipStreamSynchronize(lf->stream));
+    const char *h_out = static_cast<const char *>(lf->h_out.p);
     if (n_outside) *n_outside = (int64_t) * reinterpret_cast<const unsigned long long *>(h_out);
     if (x) std::memcpy(x, h_out + x_off, P * sizeof(double));
     if (y) std::memcpy(y, h_out + y_off, P * sizeof(double));
@@ -337,7 +269,7 @@ int rp_lift_evaluate(rp_lift *lf, const rp_params *p, int64_t K, int32_t n_poses
         if (reason_counts) std::memset(reason_counts, 0, 8 * sizeof(int64_t));
         return RP_OK;
     }
-    LF_TRY(lf, hipSetDevice(lf->device));
+    RP_TRY(lf, hipSetDevice(lf->device));
     const size_t P = (size_t)K * (size_t)n_poses, Kz = (size_t)K;
     // inputs: the six planes | theta0? [K] | len? [K]
     const size_t th0_off = 6 * P * sizeof(double), len_off = th0_off + (theta0 ? Kz * sizeof(double) : 0);
@@ -351,18 +283,15 @@ int rp_lift_evaluate(rp_lift *lf, const rp_params *p, int64_t K, int32_t n_poses
     for (int q = 0; q < LF_PLANES; ++q)
         if (outs[q]) n_back = q + 1;
     const size_t back_bytes = pl_off + (size_t)n_back * P * sizeof(double);
-    int rc;
-    if ((rc = grow(lf, lf->h_in, lf->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->d_in, lf->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->h_out, lf->cap_h_out, back_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(lf, lf->d_out, lf->cap_d_out, dev_bytes, false)) != RP_OK) return rc;
-    char *h_in = static_cast<char *>(lf->h_in);
-    const char *d_in = static_cast<const char *>(lf->d_in);
+    const int rc = grow_call(lf, "rp_lift", in_bytes, back_bytes, dev_bytes);
+    if (rc != RP_OK) return rc;
+    char *h_in = static_cast<char *>(lf->h_in.p);
+    const char *d_in = static_cast<const char *>(lf->d_in.p);
     for (int q = 0; q < 6; ++q) std::memcpy(h_in + (size_t)q * P * sizeof(double), planes[q], P * sizeof(double));
     if (theta0) std::memcpy(h_in + th0_off, theta0, Kz * sizeof(double));
     if (len) std::memcpy(h_in + len_off, len, Kz * sizeof(int32_t));
-    LF_TRY(lf, hipMemcpyAsync(lf->d_in, lf->h_in, in_bytes, hipMemcpyHostToDevice, lf->stream));
-    char *dv = static_cast<char *>(lf->d_out);
+    RP_TRY(lf, hipMemcpyAsync(lf->d_in.p, lf->h_in.p, in_bytes, hipMemcpyHostToDevice, lf->stream));
+    char *dv = static_cast<char *>(lf->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(dv);
     uint32_t *d_status = reinterpret_cast<uint32_t *>(dv + st_off);
     const LfKin kin = {p->constraint_mask, p->low_vel_mode ? 1 : 0, p->dt, p->wheelbase, p->a_max, p->v_switch, p->v_delta_max,
@@ -374,12 +303,12 @@ int rp_lift_evaluate(rp_lift *lf, const rp_params *p, int64_t K, int32_t n_poses
                        reinterpret_cast<const double *>(d_in), len ? reinterpret_cast<const int32_t *>(d_in + len_off) : nullptr,
                        theta0 ? reinterpret_cast<const double *>(d_in + th0_off) : nullptr, (long long)K, (int)n_poses,
                        reinterpret_cast<double *>(dv + pl_off), d_status);
-    LF_TRY(lf, hipGetLastError());
+    RP_TRY(lf, hipGetLastError());
     hipLaunchKernelGGL(rp_lift_final_kernel, dim3(1), dim3(LF_FINAL_BLOCK), 0, lf->stream, (long long)K, d_status, d_red);
-    LF_TRY(lf, hipGetLastError());
-    LF_TRY(lf, hipMemcpyAsync(lf->h_out, lf->d_out, back_bytes, hipMemcpyDeviceToHost, lf->stream));
-    LF_TRY(lf, hipStreamSynchronize(lf->stream));
-    const char *h_out = static_cast<const char *>(lf->h_out);
+    RP_TRY(lf, hipGetLastError());
+    RP_TRY(lf, hipMemcpyAsync(lf->h_out.p, lf->d_out.p, back_bytes, hipMemcpyDeviceToHost, lf->stream));
+    RP_TRY(lf, hipStreamSynchronize(lf->stream));
+    const char *h_out = static_cast<const char *>(lf->h_out.p);
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (first_feasible) *first_feasible = h_red[0] < (unsigned long long)K ? (int64_t)h_red[0] : -1;
     if (n_feasible) *n_feasible = (int64_t)h_red[1];

@@ -20,9 +20,10 @@
 #include <string>
 #include <vector>
 
-#include "rp_check_rules.h"   // the obstacle tables, cc.collide and both tests of a chunk: shared with rp_check.hip
+#include "rp_check_rules.h"   // the obstacle tables and their builder, cc.collide and both tests of a chunk: shared with rp_check.hip
 #include "rp_lift_rules.h"    // the segment row, the segment search, the step's checks: shared with rp_lift.hip
 #include "rp_pick_cost.h"     // the cost's scalars and the terms of a pose: shared with rp_epick.hip
+#include "rp_session.h"       // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_pick.h"
 
 namespace {
@@ -242,97 +243,21 @@ __global__ __launch_bounds__(PK_FINAL_BLOCK) void rp_pick_final_kernel(long long
 
 }  // namespace
 
-struct rp_pick {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_pick : RpSession {
     LfTable tb = {nullptr, 0, 0, 0.0, 0.0, 0.0};
     CkTables ob = {nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-    double *d_rows = nullptr, *d_stat = nullptr, *d_dyn = nullptr;
-    // inputs of a call: pinned host block and its device copy; the results on the device and a pinned host block for the part of
-    // them a call asks for.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_rows, d_stat, d_dyn;
 };
-
-namespace {
-
-int fail(rp_pick *pk, int code, const std::string &msg) {
-    pk->err = msg;
-    return code;
-}
-
-#define PK_TRY(pk, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(pk, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int grow(rp_pick *pk, void *&buf, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (buf) { PK_TRY(pk, pinned ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&buf, want, hipHostMallocDefault) : hipMalloc(&buf, want)) != hipSuccess) {
-        buf = nullptr;
-        return fail(pk, RP_ENOMEM, pinned ? "rp_pick: pinned host memory" : "rp_pick: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-// a new table beside the old one; the old one is freed only once the new one is whole
-int upload(rp_pick *pk, double *&fresh, const std::vector<double> &src) {
-    fresh = nullptr;
-    if (src.empty()) return RP_OK;
-    PK_TRY(pk, hipMalloc((void **)&fresh, src.size() * sizeof(double)));
-    const hipError_t e = hipMemcpy(fresh, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        fresh = nullptr;
-        return fail(pk, RP_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    return RP_OK;
-}
-
-size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
-
-}  // namespace
 
 extern "C" {
 
 int rp_pick_abi_version(void) { return RP_PICK_ABI_VERSION; }
 
-int rp_pick_create(rp_pick **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_pick *pk = new (std::nothrow) rp_pick();
-    if (!pk) return RP_ENOMEM;
-    *out = pk;   // returned even on failure so that rp_pick_last_error works; the caller destroys it
-    pk->device = device;
-    int ndev = 0;
-    PK_TRY(pk, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(pk, RP_EINVAL, "no such HIP device");
-    PK_TRY(pk, hipSetDevice(device));
-    PK_TRY(pk, hipStreamCreateWithFlags(&pk->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_pick_create(rp_pick **out, int device) { return session_create(out, device); }
 
-void rp_pick_destroy(rp_pick *pk) {
-    if (!pk) return;
-    (void)hipSetDevice(pk->device);
-    if (pk->stream) (void)hipStreamSynchronize(pk->stream);
-    void *dev[] = {pk->d_rows, pk->d_stat, pk->d_dyn, pk->d_in, pk->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (pk->h_in) (void)hipHostFree(pk->h_in);
-    if (pk->h_out) (void)hipHostFree(pk->h_out);
-    if (pk->stream) (void)hipStreamDestroy(pk->stream);
-    delete pk;
-}
+void rp_pick_destroy(rp_pick *pk) { session_destroy(pk); }
 
-const char *rp_pick_last_error(const rp_pick *pk) { return pk ? pk->err.c_str() : "null pick object"; }
+const char *rp_pick_last_error(const rp_pick *pk) { return session_last_error(pk, "null pick object"); }
 
 int rp_pick_set_reference(rp_pick *pk, int32_t n, const double *ref_xy, const double *ref_pos, const double *ref_theta, const double *ref_curv,
                           const double *ref_curv_d, double proj_domain_d_limit) {
@@ -340,16 +265,10 @@ int rp_pick_set_reference(rp_pick *pk, int32_t n, const double *ref_xy, const do
     if (!pk->stream) return fail(pk, RP_ESTATE, "rp_pick_set_reference: the object has no device (rp_pick_create failed)");
     std::vector<double> rows;
     std::string msg;
-    const int rc = lf_build_rows("rp_pick_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
+    int rc = lf_build_rows("rp_pick_set_reference", n, ref_xy, ref_pos, ref_theta, ref_curv, ref_curv_d, proj_domain_d_limit, rows, msg);
     if (rc != RP_OK) return fail(pk, rc, msg);
-    PK_TRY(pk, hipSetDevice(pk->device));
-    PK_TRY(pk, hipStreamSynchronize(pk->stream));
-    double *fresh = nullptr;
-    int up;
-    if ((up = upload(pk, fresh, rows)) != RP_OK) return up;
-    if (pk->d_rows) (void)hipFree(pk->d_rows);
-    pk->d_rows = fresh;
-    pk->tb = {pk->d_rows, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
+    if ((rc = replace_tables(pk, {{&pk->d_rows, &rows}})) != RP_OK) return rc;
+    pk->tb = {pk->d_rows.p, n - 1, lf_search_iters(n), ref_pos[0], ref_pos[n - 1], proj_domain_d_limit};
     return RP_OK;
 }
 
@@ -359,23 +278,11 @@ int rp_pick_set_obstacles(rp_pick *pk, int32_t n_sobb, const double *sobb, int32
     if (!pk->stream) return fail(pk, RP_ESTATE, "rp_pick_set_obstacles: the object has no device (rp_pick_create failed)");
     std::vector<double> a, e;
     std::string msg;
-    const int rc = ck_build_tables("rp_pick_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
+    int rc = ot_build("rp_pick_set_obstacles", n_sobb, sobb, n_tri, tri, n_circ, circ, n_dyn, n_steps, dyn, a, e, msg);
     if (rc != RP_OK) return fail(pk, rc, msg);
-    PK_TRY(pk, hipSetDevice(pk->device));
-    PK_TRY(pk, hipStreamSynchronize(pk->stream));
-    double *stat = nullptr, *dynp = nullptr;
-    int up;
-    if ((up = upload(pk, stat, a)) != RP_OK) return up;
-    if ((up = upload(pk, dynp, e)) != RP_OK) {
-        if (stat) (void)hipFree(stat);
-        return up;
-    }
-    if (pk->d_stat) (void)hipFree(pk->d_stat);
-    if (pk->d_dyn) (void)hipFree(pk->d_dyn);
-    pk->d_stat = stat;
-    pk->d_dyn = dynp;
-    const bool any_dyn = n_dyn > 0 && n_steps > 0;
-    pk->ob = {pk->d_stat, pk->d_dyn, n_sobb, n_tri, n_circ, any_dyn ? n_dyn : 0, any_dyn ? n_steps : 0, dyn_t0};
+    if ((rc = replace_tables(pk, {{&pk->d_stat, &a}, {&pk->d_dyn, &e}})) != RP_OK) return rc;
+    const bool any_dyn = !e.empty();
+    pk->ob = {pk->d_stat.p, pk->d_dyn.p, n_sobb, n_tri, n_circ, any_dyn ? n_dyn : 0, any_dyn ? n_steps : 0, dyn_t0};
     return RP_OK;
 }
 
@@ -421,7 +328,7 @@ int rp_pick_select(rp_pick *pk, const rp_params *p, const rp_cost *cost, uint32_
             for (size_t q = 0; q < (size_t)RP_N_ARRAYS * nz; ++q) best_states[q] = std::nan("");
         return RP_OK;
     }
-    PK_TRY(pk, hipSetDevice(pk->device));
+    RP_TRY(pk, hipSetDevice(pk->device));
     const size_t P = (size_t)K * nz, Kz = (size_t)K;
     // inputs: the six planes | theta0? [K] | len? [K]
     const size_t th0_off = 6 * P * sizeof(double), len_off = th0_off + (theta0 ? Kz * sizeof(double) : 0);
@@ -440,18 +347,15 @@ int rp_pick_select(rp_pick *pk, const rp_params *p, const rp_cost *cost, uint32_
     const size_t front_bytes = first_segment_hit ? pl_off : first_pose_hit ? fs_off : status ? fp_off : cost_out ? st_off : best_states ? cost_off : blk_off;
     const size_t pl_bytes = pl_end > pl_first ? (size_t)(pl_end - pl_first) * P * sizeof(double) : 0;
     const size_t h_pl_off = align8(front_bytes);
-    int rc;
-    if ((rc = grow(pk, pk->h_in, pk->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(pk, pk->d_in, pk->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(pk, pk->h_out, pk->cap_h_out, h_pl_off + pl_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(pk, pk->d_out, pk->cap_d_out, dev_bytes, false)) != RP_OK) return rc;
-    char *h_in = static_cast<char *>(pk->h_in);
-    const char *d_in = static_cast<const char *>(pk->d_in);
+    const int rc = grow_call(pk, "rp_pick", in_bytes, h_pl_off + pl_bytes, dev_bytes);
+    if (rc != RP_OK) return rc;
+    char *h_in = static_cast<char *>(pk->h_in.p);
+    const char *d_in = static_cast<const char *>(pk->d_in.p);
     for (int q = 0; q < 6; ++q) std::memcpy(h_in + (size_t)q * P * sizeof(double), planes[q], P * sizeof(double));
     if (theta0) std::memcpy(h_in + th0_off, theta0, Kz * sizeof(double));
     if (len) std::memcpy(h_in + len_off, len, Kz * sizeof(int32_t));
-    PK_TRY(pk, hipMemcpyAsync(pk->d_in, pk->h_in, in_bytes, hipMemcpyHostToDevice, pk->stream));
-    char *dv = static_cast<char *>(pk->d_out);
+    RP_TRY(pk, hipMemcpyAsync(pk->d_in.p, pk->h_in.p, in_bytes, hipMemcpyHostToDevice, pk->stream));
+    char *dv = static_cast<char *>(pk->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(dv);
     double *d_block = reinterpret_cast<double *>(dv + blk_off), *d_cost = reinterpret_cast<double *>(dv + cost_off);
     uint32_t *d_status = reinterpret_cast<uint32_t *>(dv + st_off);
@@ -470,9 +374,9 @@ int rp_pick_select(rp_pick *pk, const rp_params *p, const rp_cost *cost, uint32_
     const size_t lds_bytes = rows_in_lds ? (size_t)pk->tb.n_seg * LF_ROW * sizeof(double) : 0;
     hipLaunchKernelGGL(lift, dim3((unsigned)((K + PK_WAVES - 1) / PK_WAVES)), dim3(PK_BLOCK), lds_bytes, pk->stream, pk->tb, kin, cc, d_six, d_len, d_th0,
                        (long long)K, (int)n_poses, (const unsigned long long *)nullptr, (double *)nullptr, all, d_status, d_cost);
-    PK_TRY(pk, hipGetLastError());
+    RP_TRY(pk, hipGetLastError());
     if (mode != 0) {
-        PK_TRY(pk, hipMemsetAsync(d_first_pose, 0x7f, 2 * Kz * sizeof(int32_t), pk->stream));
+        RP_TRY(pk, hipMemsetAsync(d_first_pose, 0x7f, 2 * Kz * sizeof(int32_t), pk->stream));
         const int nchunk = (n_poses + 63) / 64;
         const long long waves = (long long)K * nchunk;
         const bool shapes_in_lds = pk->ob.n_sobb + pk->ob.n_tri + pk->ob.n_circ <= PK_CK_LDS_ROWS;
@@ -480,22 +384,22 @@ int rp_pick_select(rp_pick *pk, const rp_params *p, const rp_cost *cost, uint32_
         hipLaunchKernelGGL(collide, dim3((unsigned)((waves + PK_WAVES - 1) / PK_WAVES)), dim3(PK_BLOCK), 0, pk->stream, pk->ob, d_planes, d_len, d_status,
                            (int)K, (int)n_poses, nchunk, mode, p->wb_rear_axle, 0.5 * p->length, 0.5 * p->width, (int)p->time_step0, (int)p->factor,
                            d_first_pose, d_first_seg);
-        PK_TRY(pk, hipGetLastError());
+        RP_TRY(pk, hipGetLastError());
     }
     hipLaunchKernelGGL(rp_pick_final_kernel, dim3(1), dim3(PK_FINAL_BLOCK), 0, pk->stream, (long long)K, mode, d_status, d_cost, d_first_pose, d_first_seg, d_red);
-    PK_TRY(pk, hipGetLastError());
+    RP_TRY(pk, hipGetLastError());
     if (best_states) {
         PkPlanes rows;
         for (int q = 0; q < LF_PLANES; ++q) rows.plane[q] = d_block + (size_t)PK_PLANE_ROW[q] * nz;
         hipLaunchKernelGGL(lift, dim3(1), dim3(PK_BLOCK), lds_bytes, pk->stream, pk->tb, kin, cc, d_six, d_len, d_th0, (long long)K, (int)n_poses,
                            (const unsigned long long *)d_red, d_block, rows, (uint32_t *)nullptr, (double *)nullptr);
-        PK_TRY(pk, hipGetLastError());
+        RP_TRY(pk, hipGetLastError());
     }
-    char *h_out = static_cast<char *>(pk->h_out);
-    PK_TRY(pk, hipMemcpyAsync(h_out, dv, front_bytes, hipMemcpyDeviceToHost, pk->stream));
+    char *h_out = static_cast<char *>(pk->h_out.p);
+    RP_TRY(pk, hipMemcpyAsync(h_out, dv, front_bytes, hipMemcpyDeviceToHost, pk->stream));
     if (pl_bytes)
-        PK_TRY(pk, hipMemcpyAsync(h_out + h_pl_off, dv + pl_off + (size_t)pl_first * P * sizeof(double), pl_bytes, hipMemcpyDeviceToHost, pk->stream));
-    PK_TRY(pk, hipStreamSynchronize(pk->stream));
+        RP_TRY(pk, hipMemcpyAsync(h_out + h_pl_off, dv + pl_off + (size_t)pl_first * P * sizeof(double), pl_bytes, hipMemcpyDeviceToHost, pk->stream));
+    RP_TRY(pk, hipStreamSynchronize(pk->stream));
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     if (result) {
         const bool any = h_red[RED_BEST] < (unsigned long long)K;

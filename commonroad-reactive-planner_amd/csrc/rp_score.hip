@@ -15,6 +15,7 @@
 
 #include "rp_device.h"
 #include "rp_frontend.h"
+#include "rp_session.h"   // the host session: the object's first fields, fail, RP_TRY, the blocks of a call, the upload of a table
 #include "../../include/rp_score.h"
 
 namespace {
@@ -383,46 +384,12 @@ __global__ __launch_bounds__(SC_FINAL_BLOCK) void rp_score_outside_kernel(long l
 
 }  // namespace
 
-struct rp_score {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct rp_score : RpSession {
     ScTable tb = {nullptr, 0, 0.0};
-    double *d_rows = nullptr;
-    // inputs of a call: pinned host block and its device copy; the results on the device and a pinned host block for the part of
-    // them a call asks for.  They grow on demand.
-    void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_h_in = 0, cap_d_in = 0, cap_h_out = 0, cap_d_out = 0;
+    RpTable d_rows;
 };
 
 namespace {
-
-int fail(rp_score *sc, int code, const std::string &msg) {
-    sc->err = msg;
-    return code;
-}
-
-#define SC_TRY(sc, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(sc, RP_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-int grow(rp_score *sc, void *&buf, size_t &cap, size_t need, bool pinned) {
-    if (need <= cap) return RP_OK;
-    if (buf) { SC_TRY(sc, pinned ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; }
-    cap = 0;
-    const size_t want = need < 65536 ? 65536 : need + need / 4;
-    if ((pinned ? hipHostMalloc(&buf, want, hipHostMallocDefault) : hipMalloc(&buf, want)) != hipSuccess) {
-        buf = nullptr;
-        return fail(sc, RP_ENOMEM, pinned ? "rp_score: pinned host memory" : "rp_score: device memory");
-    }
-    cap = want;
-    return RP_OK;
-}
-
-size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 // launch of the pose kernel over K trajectories of n poses
 void launch_pose(rp_score *sc, const ScKin &kin, const double *x, const double *y, const double *theta, const double *v, const double *a,
@@ -444,35 +411,11 @@ extern "C" {
 
 int rp_score_abi_version(void) { return RP_SCORE_ABI_VERSION; }
 
-int rp_score_create(rp_score **out, int device) {
-    if (!out) return RP_EINVAL;
-    *out = nullptr;
-    rp_score *sc = new (std::nothrow) rp_score();
-    if (!sc) return RP_ENOMEM;
-    *out = sc;   // returned even on failure so that rp_score_last_error works; the caller destroys it
-    sc->device = device;
-    int ndev = 0;
-    SC_TRY(sc, hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(sc, RP_EINVAL, "no such HIP device");
-    SC_TRY(sc, hipSetDevice(device));
-    SC_TRY(sc, hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
-    return RP_OK;
-}
+int rp_score_create(rp_score **out, int device) { return session_create(out, device); }
 
-void rp_score_destroy(rp_score *sc) {
-    if (!sc) return;
-    (void)hipSetDevice(sc->device);
-    if (sc->stream) (void)hipStreamSynchronize(sc->stream);
-    void *dev[] = {sc->d_rows, sc->d_in, sc->d_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (sc->h_in) (void)hipHostFree(sc->h_in);
-    if (sc->h_out) (void)hipHostFree(sc->h_out);
-    if (sc->stream) (void)hipStreamDestroy(sc->stream);
-    delete sc;
-}
+void rp_score_destroy(rp_score *sc) { session_destroy(sc); }
 
-const char *rp_score_last_error(const rp_score *sc) { return sc ? sc->err.c_str() : "null score object"; }
+const char *rp_score_last_error(const rp_score *sc) { return session_last_error(sc, "null score object"); }
 
 int rp_score_set_reference(rp_score *sc, int32_t n, const double *ref_xy, const double *ref_pos, const double *ref_theta, double proj_domain_d_limit) {
     if (!sc) return RP_EINVAL;
@@ -488,8 +431,6 @@ int rp_score_set_reference(rp_score *sc, int32_t n, const double *ref_xy, const 
         if (ref_xy[2 * (size_t)i] == ref_xy[2 * (size_t)i + 2] && ref_xy[2 * (size_t)i + 1] == ref_xy[2 * (size_t)i + 3])
             return fail(sc, RP_EINVAL, "rp_score_set_reference: zero-length segment " + std::to_string(i));
     }
-    SC_TRY(sc, hipSetDevice(sc->device));
-    SC_TRY(sc, hipStreamSynchronize(sc->stream));
     std::vector<double> rows;
     std::vector<rpfe::Pt> ref, tan;
     try {
@@ -512,11 +453,9 @@ int rp_score_set_reference(rp_score *sc, int32_t n, const double *ref_xy, const 
         for (int q = 0; q < SC_ROW; ++q)
             if (!std::isfinite(r[q])) return fail(sc, RP_EINVAL, "rp_score_set_reference: segment " + std::to_string(k) + " is not finite");
     }
-    sc->tb = {nullptr, 0, 0.0};   // (a failed upload leaves no table, never half of the new one)
-    if (sc->d_rows) { SC_TRY(sc, hipFree(sc->d_rows)); sc->d_rows = nullptr; }
-    SC_TRY(sc, hipMalloc((void **)&sc->d_rows, rows.size() * sizeof(double)));
-    SC_TRY(sc, hipMemcpy(sc->d_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    sc->tb = {sc->d_rows, n - 1, proj_domain_d_limit};
+    const int rc = replace_tables(sc, {{&sc->d_rows, &rows}});
+    if (rc != RP_OK) return rc;
+    sc->tb = {sc->d_rows.p, n - 1, proj_domain_d_limit};
     return RP_OK;
 }
 
@@ -530,35 +469,32 @@ int rp_score_project(rp_score *sc, int64_t n_points, const double *x, const doub
         if (n_outside) *n_outside = 0;
         return RP_OK;
     }
-    SC_TRY(sc, hipSetDevice(sc->device));
+    RP_TRY(sc, hipSetDevice(sc->device));
     const size_t P = (size_t)n_points;
     const size_t in_bytes = 2 * P * sizeof(double);
     // results on the device: scalar | s [P] | d [P] | segment [P]
     const size_t s_off = 8 * sizeof(unsigned long long), d_off = s_off + P * sizeof(double), seg_off = d_off + P * sizeof(double);
     const size_t out_bytes = seg_off + P * sizeof(int32_t);
-    int rc;
-    if ((rc = grow(sc, sc->h_in, sc->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->d_in, sc->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->h_out, sc->cap_h_out, out_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->d_out, sc->cap_d_out, out_bytes, false)) != RP_OK) return rc;
-    double *h_in = static_cast<double *>(sc->h_in);
+    const int rc = grow_call(sc, "rp_score", in_bytes, out_bytes, out_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_in = static_cast<double *>(sc->h_in.p);
     std::memcpy(h_in, x, P * sizeof(double));
     std::memcpy(h_in + P, y, P * sizeof(double));
-    SC_TRY(sc, hipMemcpyAsync(sc->d_in, sc->h_in, in_bytes, hipMemcpyHostToDevice, sc->stream));
-    const double *d_x = static_cast<const double *>(sc->d_in);
-    char *d_out = static_cast<char *>(sc->d_out);
+    RP_TRY(sc, hipMemcpyAsync(sc->d_in.p, sc->h_in.p, in_bytes, hipMemcpyHostToDevice, sc->stream));
+    const double *d_x = static_cast<const double *>(sc->d_in.p);
+    char *d_out = static_cast<char *>(sc->d_out.p);
     int32_t *d_seg = reinterpret_cast<int32_t *>(d_out + seg_off);
     const ScKin kin = {0u, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};
     // the flat batch as ONE trajectory of n_points poses: wavefront w = points 64 w .. 64 w + 63
     launch_pose(sc, kin, d_x, d_x + P, nullptr, nullptr, nullptr, nullptr, nullptr, 1, (int)n_points, false, reinterpret_cast<double *>(d_out + s_off),
                 reinterpret_cast<double *>(d_out + d_off), nullptr, d_seg, nullptr);
-    SC_TRY(sc, hipGetLastError());
+    RP_TRY(sc, hipGetLastError());
     hipLaunchKernelGGL(rp_score_outside_kernel, dim3(1), dim3(SC_FINAL_BLOCK), 0, sc->stream, (long long)n_points, d_seg,
                        reinterpret_cast<unsigned long long *>(d_out));
-    SC_TRY(sc, hipGetLastError());
-    SC_TRY(sc, hipMemcpyAsync(sc->h_out, sc->d_out, out_bytes, hipMemcpyDeviceToHost, sc->stream));
-    SC_TRY(sc, hipStreamSynchronize(sc->stream));
-    const char *h_out = static_cast<const char *>(sc->h_out);
+    RP_TRY(sc, hipGetLastError());
+    RP_TRY(sc, hipMemcpyAsync(sc->h_out.p, sc->d_out.p, out_bytes, hipMemcpyDeviceToHost, sc->stream));
+    RP_TRY(sc, hipStreamSynchronize(sc->stream));
+    const char *h_out = static_cast<const char *>(sc->h_out.p);
     if (n_outside) *n_outside = (int64_t) * reinterpret_cast<const unsigned long long *>(h_out);
     if (s) std::memcpy(s, h_out + s_off, P * sizeof(double));
     if (d) std::memcpy(d, h_out + d_off, P * sizeof(double));
@@ -608,7 +544,7 @@ int rp_score_evaluate(rp_score *sc, const rp_params *p, const rp_cost *cost, int
         if (reason_counts) std::memset(reason_counts, 0, 8 * sizeof(int64_t));
         return RP_OK;
     }
-    SC_TRY(sc, hipSetDevice(sc->device));
+    RP_TRY(sc, hipSetDevice(sc->device));
     const size_t P = (size_t)K * (size_t)n_poses, Kz = (size_t)K;
     // inputs: x | y | theta | a | v? | kappa? | len?
     const int n_planes = 4 + (v ? 1 : 0) + (kappa ? 1 : 0);
@@ -620,13 +556,10 @@ int rp_score_evaluate(rp_score *sc, const rp_params *p, const rp_cost *cost, int
     const size_t code_off = th_off + P * sizeof(double);
     const size_t dev_bytes = code_off + P;
     const size_t back_bytes = theta_cl_out ? code_off : d_out ? th_off : s_out ? d_off : s_off;
-    int rc;
-    if ((rc = grow(sc, sc->h_in, sc->cap_h_in, in_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->d_in, sc->cap_d_in, in_bytes, false)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->h_out, sc->cap_h_out, back_bytes, true)) != RP_OK) return rc;
-    if ((rc = grow(sc, sc->d_out, sc->cap_d_out, dev_bytes, false)) != RP_OK) return rc;
-    double *h_in = static_cast<double *>(sc->h_in);
-    const double *d_in = static_cast<const double *>(sc->d_in);
+    const int rc = grow_call(sc, "rp_score", in_bytes, back_bytes, dev_bytes);
+    if (rc != RP_OK) return rc;
+    double *h_in = static_cast<double *>(sc->h_in.p);
+    const double *d_in = static_cast<const double *>(sc->d_in.p);
     int plane = 0;
     auto put = [&](const double *src) -> const double * {
         if (!src) return nullptr;
@@ -639,8 +572,8 @@ int rp_score_evaluate(rp_score *sc, const rp_params *p, const rp_cost *cost, int
         std::memcpy(h_in + (size_t)plane * P, len, Kz * sizeof(int32_t));
         d_len = reinterpret_cast<const int32_t *>(d_in + (size_t)plane * P);
     }
-    SC_TRY(sc, hipMemcpyAsync(sc->d_in, sc->h_in, in_bytes, hipMemcpyHostToDevice, sc->stream));
-    char *dv = static_cast<char *>(sc->d_out);
+    RP_TRY(sc, hipMemcpyAsync(sc->d_in.p, sc->h_in.p, in_bytes, hipMemcpyHostToDevice, sc->stream));
+    char *dv = static_cast<char *>(sc->d_out.p);
     unsigned long long *d_red = reinterpret_cast<unsigned long long *>(dv);
     double *d_cost = reinterpret_cast<double *>(dv + cost_off), *d_s = reinterpret_cast<double *>(dv + s_off);
     double *d_d = reinterpret_cast<double *>(dv + d_off), *d_thcl = reinterpret_cast<double *>(dv + th_off);
@@ -649,18 +582,18 @@ int rp_score_evaluate(rp_score *sc, const rp_params *p, const rp_cost *cost, int
     const ScKin kin = {cm, p->dt, p->wheelbase, p->a_max, p->v_switch, p->v_delta_max, std::tan(p->delta_max) / p->wheelbase};
     launch_pose(sc, kin, d_x, d_y, d_th, d_v, d_a, d_kappa, d_len, (long long)K, (int)n_poses, (flags & RP_SCORE_EXHAUSTIVE) != 0, d_s, d_d, d_thcl, nullptr,
                 d_code);
-    SC_TRY(sc, hipGetLastError());
+    RP_TRY(sc, hipGetLastError());
     // cost_function.py:82-92: the fail-safe cost is the default one with w_a = 1, desired_d = 0 and no v / s terms
     const ScCost cc = {has_speed ? 1 : 0, has_s ? 1 : 0, failsafe ? 1.0 : cost->w_a, has_speed ? cost->desired_speed : 0.0, failsafe ? 0.0 : cost->desired_d,
                        has_s ? cost->desired_s : 0.0};
     hipLaunchKernelGGL(rp_score_traj_kernel, dim3((unsigned)((K + SC_WAVES - 1) / SC_WAVES)), dim3(SC_BLOCK), 0, sc->stream, (long long)K, (int)n_poses, d_len,
                        d_code, d_s, d_d, d_thcl, d_v, d_a, cc, d_status, d_cost);
-    SC_TRY(sc, hipGetLastError());
+    RP_TRY(sc, hipGetLastError());
     hipLaunchKernelGGL(rp_score_final_kernel, dim3(1), dim3(SC_FINAL_BLOCK), 0, sc->stream, (long long)K, d_status, d_cost, d_red);
-    SC_TRY(sc, hipGetLastError());
-    SC_TRY(sc, hipMemcpyAsync(sc->h_out, sc->d_out, back_bytes, hipMemcpyDeviceToHost, sc->stream));
-    SC_TRY(sc, hipStreamSynchronize(sc->stream));
-    const char *h_out = static_cast<const char *>(sc->h_out);
+    RP_TRY(sc, hipGetLastError());
+    RP_TRY(sc, hipMemcpyAsync(sc->h_out.p, sc->d_out.p, back_bytes, hipMemcpyDeviceToHost, sc->stream));
+    RP_TRY(sc, hipStreamSynchronize(sc->stream));
+    const char *h_out = static_cast<const char *>(sc->h_out.p);
     const unsigned long long *h_red = reinterpret_cast<const unsigned long long *>(h_out);
     const bool any = h_red[0] < (unsigned long long)K;
     if (best) *best = any ? (int64_t)h_red[0] : -1;

@@ -26,7 +26,8 @@ EXPORTS = ["rp_epick_abi_version", "rp_epick_create", "rp_epick_destroy", "rp_ep
            "rp_epick_set_reference", "rp_epick_set_static"]
 RESULT_FIELDS = ["struct_size", "reserved_", "best", "best_cost", "n_feasible", "n_collision", "n_collision_before_best", "reason_counts", "best_members_hit",
                  "best_risk"]
-PROTECTED = ["rp_check.hip", "rp_ensemble.hip", "rp_clearance.hip", "rp_check_rules.h", "rp_lift_rules.h", "rp_lift_walk.inc", "rp_lift.hip", "rp_score.hip"]
+PROTECTED = ["rp_check.hip", "rp_ensemble.hip", "rp_clearance.hip", "rp_check_rules.h", "rp_lift_rules.h", "rp_lift_walk.inc", "rp_lift.hip", "rp_score.hip",
+             "rp_session.h", "rp_obstacle_tables.h", "../commonroad_rp_amd/_session.py"]
 
 
 def _header():

@@ -113,7 +113,8 @@ def test_makefile_targets_and_source_hash_inputs_untouched():
     assert re.search(r"^\$\(LIFTLIB\): rp_lift\.hip rp_device\.h rp_math\.h rp_frontend\.h \.\./\.\./include/rp_lift\.h \.\./\.\./include/rp_amd\.h$", mk, flags=re.M)
     assert re.search(r"^clean:\n\trm -f .*\$\(LIFTLIB\)", mk, flags=re.M)
     # the files behind rp_source_hash() and the four sibling libraries are only included: the lift defines nothing in them
-    for name in srcs.split() + ["rp_check.hip", "rp_ensemble.hip", "rp_clearance.hip", "rp_score.hip"]:
+    # (nor in what the libraries' host sides and bindings share)
+    for name in srcs.split() + ["rp_check.hip", "rp_ensemble.hip", "rp_clearance.hip", "rp_score.hip", "rp_session.h", "rp_obstacle_tables.h", "../commonroad_rp_amd/_session.py"]:
         text = open(os.path.join(CSRC, name)).read()
         assert "rp_lift" not in text and "LF_LDS_ROWS" not in text, name
 

@@ -130,7 +130,7 @@ def test_makefile_targets_source_hash_inputs_and_capacities():
     assert re.search(r"^PICKDEPS\s*:=.* rp_lift_rules\.h rp_lift_walk\.inc ", mk, flags=re.M)
     # the files behind rp_source_hash() and the sibling libraries' own sources define nothing of the pick
     for name in srcs.split() + ["rp_check.hip", "rp_ensemble.hip", "rp_clearance.hip", "rp_score.hip", "rp_lift.hip", "rp_check_rules.h", "rp_lift_rules.h",
-                               "rp_lift_walk.inc"]:
+                               "rp_lift_walk.inc", "rp_session.h", "rp_obstacle_tables.h", "../commonroad_rp_amd/_session.py"]:
         text = open(os.path.join(P.CSRC, name)).read()
         assert "rp_pick_" not in text and "PK_" not in text, name
     # the capacities at which the pick switches to its device-memory variants are the siblings'
