@@ -389,11 +389,20 @@ def evaluate_planes(c: Case, planes, traj_len):
 
 def _from_planes(c, s, s_vel, s_acc, d, d_vel, d_acc, tl):
     """reactive_planner.py:776-960 from the six curvilinear planes on"""
-    p, tb, cst = c.inp.params, c.tables, c.inp.cost
-    n, m = p.N + 1, len(tl)
-    dt = DD(LD(p.dt))
-    low = bool(p.low_vel_mode)
+    p = c.inp.params
+    n = p.N + 1
     valid = np.arange(n)[None, :] < tl[:, None]
+    st, inter = per_pose(bool(p.low_vel_mode), c.tables, s, s_vel, s_acc, d, d_vel, d_acc, valid, LD(p.x0_orientation))
+    _enlarge(st, tl, n, DD(LD(p.dt)))
+    return np.stack([st[r].ld() for r in range(14)], axis=1), _cost(c.inp.cost, st, n).ld(), {key: val.ld() for key, val in inter.items()}
+
+
+def per_pose(low, tb, s, s_vel, s_acc, d, d_vel, d_acc, valid, theta0):
+    """reactive_planner.py:776-960 pose by pose, outside a planner case (tests/_liftx.py: what the lift computes from given planes): the
+    six double-word planes [m, n], ``valid`` [m, n] the poses of each trajectory, ``tb`` the tables (ref_pos, ref_theta, ref_curv,
+    ref_curv_d, ref_x, ref_y: doubles), ``theta0`` the orientation a standstill from pose 0 keeps, a longdouble or [m] of them.  No
+    horizon extension, no cost -> (the fourteen rows, a dict of double-word arrays, zero outside ``valid``; the intermediates)"""
+    m, n = valid.shape
     z = lambda a: dd.where(valid, a, 0)
     s_vel = dd.where(abs(s_vel) < DD(EPS), 0, s_vel)
     d_vel = dd.where(abs(d_vel) < DD(EPS), 0, d_vel)
@@ -411,14 +420,15 @@ def _from_planes(c, s, s_vel, s_acc, d, d_vel, d_acc, tl):
     k = np.clip(np.where(s < rp[k], k - 1, k), 0, nr - 2)   # (s.hi on a vertex, s below it)
     seg = rp[k + 1] - rp[k]
     lam = (s - rp[k]) / seg
-    th_ref = _valid_orientation((rth[k + 1] - rth[k]) * (s - rp[k]) / seg + rth[k])
+    th_table = (rth[k + 1] - rth[k]) * (s - rp[k]) / seg + rth[k]
+    th_ref = _valid_orientation(th_table)
     theta_cl = dd.atan(dp)        # np.arctan2(dp, 1.0)
     theta = theta_cl + th_ref
     use = moving | low
     if not use[valid].all():   # the standstill branch carries theta from the step before
         theta = theta.copy()
         for i in range(n):
-            prev = dd.broadcast_to(DD(LD(p.x0_orientation)), (m,)) if i == 0 else theta[:, i - 1]
+            prev = dd.broadcast_to(DD(theta0), (m,)) if i == 0 else theta[:, i - 1]
             theta[:, i] = dd.where(use[:, i], theta[:, i], prev)
         theta_cl = dd.where(use, theta_cl, theta - th_ref)
     k_r = (rk[k + 1] - rk[k]) * lam + rk[k]
@@ -441,9 +451,8 @@ def _from_planes(c, s, s_vel, s_acc, d, d_vel, d_acc, tl):
     kd = dd.zeros((m, n))
     kd[:, 1:] = st[KAPPA][:, 1:] - st[KAPPA][:, :-1]   # np.diff over the padded array
     st[KAPPA_DOT] = kd
-    _enlarge(st, tl, n, dt)
-    inter = {key: val.ld() for key, val in dict(s=s, d=d, dp=dp, dpp=dpp, k_r=k_r, k_r_d=k_r_d, theta_cl=theta_cl, one_krd=one_krd, cos=cos_t).items()}
-    return np.stack([st[r].ld() for r in range(14)], axis=1), _cost(cst, st, n).ld(), inter
+    inter = dict(s=s, d=d, dp=dp, dpp=dpp, k_r=k_r, k_r_d=k_r_d, theta_cl=theta_cl, one_krd=one_krd, cos=cos_t, th_table=th_table)
+    return st, inter
 
 
 def _enlarge(st, tl, n, dt):
